@@ -17,7 +17,9 @@ selection), the three losses, backward, gradient all-reduce (N > 1) and the SGD 
 Workload per GPU = BASELINE.json configs[1]: 4 videos x 8 proposals x 9 segments = 288 RGB frames
 of 224x224 (weak scaling: per-GPU work is fixed as N grows).
 
-Rank 0 prints ONE JSON line.  `roofline` is the MFMA roofline of the dominant kernel family (the
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times --steps steps and prints it (`value`, `ms_per_step`, ...);
+`--dump-outputs DIR` also writes what the last timed step computed as DIR/<name>.npy.  Everything else below is measured only
+with `--full`, after the timed region.  `roofline` is the MFMA roofline of the dominant kernel family (the
 planes implicit-GEMM convolutions `conv_pl_kernel` / `conv_pl9_kernel`, 3 f16 MFMA products per multiply,
 forward + dgrad launches), measured live with HIP events around every launch of the same K steps (re-run eagerly right after the timed region, because events cannot be
 recorded inside a hipGraph replay); `roofline_detail` lists every conv kernel family; `cpu_baseline` times the CPU oracle
@@ -46,6 +48,7 @@ FWD_GFLOP_PER_IMAGE = {"RGB": 4.063152128, "Flow": 4.613883904}  # 2 * conv MACs
 # conv1 (7x7/2, 64 outputs of 112x112): 2 * Cin * 49 * 64 * 112^2 flop that a dgrad would cost and nobody needs
 CONV1_DGRAD_GFLOP_PER_IMAGE = {"RGB": 2 * 3 * 49 * 64 * 112 * 112 / 1e9, "Flow": 2 * 10 * 49 * 64 * 112 * 112 / 1e9}
 HBM_PEAK_GBPS = 8000.0          # MI355X_MICROARCH.md: 8 TB/s spec (6.29 TB/s measured float4 copy)
+DUMP_SAMPLE = 1 << 20           # --dump-outputs: elements kept of a larger array (4 MiB of float32)
 
 
 def parse():
@@ -57,7 +60,7 @@ def parse():
     ap.add_argument("--modality", default="RGB", choices=["RGB", "Flow"])
     ap.add_argument("--num-class", type=int, default=20)
     ap.add_argument("--cpu-baseline-videos", type=int, default=4,
-                    help="videos in the CPU-oracle sample (default: the full config-2 batch, 4 videos = 32 proposals; "
+                    help="--full: videos in the CPU-oracle sample (default: the full config-2 batch, 4 videos = 32 proposals; "
                          "0 disables the cpu_baseline leg)")
     ap.add_argument("--cpu-baseline-reps", type=int, default=3, help="timed repetitions of the CPU sample (median)")
     ap.add_argument("--bn-mode", default="frozen", choices=["frozen", "partial", "full"],
@@ -69,7 +72,7 @@ def parse():
                     help="N > 1: 'separate' = graph(fwd+bwd) -> eager RCCL all-reduce of the flat gradient -> graph(SGD), "
                          "the well-trodden path; 'overlapped' = bucketed all-reduces issued from inside the backward and "
                          "captured in the one step graph (overlaps the ~0.5 ms ring with the remaining backward)")
-    ap.add_argument("--no-kernel-events", action="store_true", help="skip per-launch HIP event timing")
+    ap.add_argument("--no-kernel-events", action="store_true", help="--full: skip per-launch HIP event timing")
     ap.add_argument("--single-stream", action="store_true",
                     help="profiling aid: no side streams (weight-gradient chain, forward branches), so that with --no-graph "
                          "every kernel runs alone and rocprofv3's per-kernel durations are free of mutual slow-down")
@@ -91,9 +94,31 @@ def parse():
                          "frame count (ticks every 6 frames, ssn_dataset.py:393-396) and its own proposals instead of --ticks / --proposals "
                          "random ones.  tests/golden/proposal_list_processed.txt is the committed excerpt of the ActivityNet-1.2 list")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="N = 1, default configuration: do not append the short secondary runs (config 3 = Flow training, config 5 = "
+                    help="--full, N = 1, default configuration: do not append the short secondary runs (config 3 = Flow training, config 5 = "
                          "Inception-v3 dense testing on the committed ActivityNet excerpt) under `secondary`")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure / check everything beyond the headline figure, after the timed region: per-launch HIP events "
+                         "(roofline, roofline_detail, hbm_kernels), cpu_baseline + parity against the CPU oracle, the standalone "
+                         "all-reduce (N > 1) and the secondary runs.  Without it a run sets up, warms up, times --steps steps, "
+                         "dumps (--dump-outputs) and prints the result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32; arrays "
+                         "larger than %d elements as a fixed, seeded sample)" % DUMP_SAMPLE)
     return ap.parse_args()
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per tensor, float32 (float64 stays float64).  An array of more than DUMP_SAMPLE elements
+    is written as the elements of its flattened form at DUMP_SAMPLE fixed, seeded positions (ascending), so that two runs with the
+    same arguments -- two builds of the project -- can be compared output for output."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a if a.dtype == np.float64 else a.astype(np.float32)
+        if a.size > DUMP_SAMPLE:
+            a = a.reshape(-1)[np.sort(np.random.RandomState(0).choice(a.size, DUMP_SAMPLE, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def self_launch(n):
@@ -133,10 +158,10 @@ def self_launch(n):
 
 
 def run_secondary(extra, timeout):
-    """One secondary configuration in its own process (`python bench.py <extra> --no-secondary`): the fields of its JSON line that
-    say what ran, how fast, against which roofline and how close to the oracle."""
+    """One secondary configuration in its own process (`python bench.py <extra> --full --no-secondary`): the fields of its JSON line
+    that say what ran, how fast, against which roofline and how close to the oracle."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__)] + list(extra) + ["--no-secondary"]
+    cmd = [sys.executable, os.path.abspath(__file__)] + list(extra) + ["--full", "--no-secondary"]
     t0 = time.perf_counter()
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE")}
     try:
@@ -250,9 +275,13 @@ def dense_test_main(args, world, rank, local_rank):
     ticks_done = 0
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        ticks_done += one_video()[1]
+        scores, t = one_video()
+        ticks_done += t
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {n_: s_ for n_, s_ in zip(("act_scores", "comp_scores", "reg_scores", "frame_output"), scores)
+                                         if s_ is not None})
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -275,7 +304,7 @@ def dense_test_main(args, world, rank, local_rank):
                                   args.tick_batch, net.test_fc.out_features) + list_note,
                    "parallelism": "replicas%d" % world, "layout": net.base_model.layout},
     }
-    if rank == 0:
+    if rank == 0 and args.full:
         # roofline of the dominant kernel family: the forward convolutions of one more video, HIP events per launch
         prof = []
         net.base_model.profiler = prof
@@ -327,6 +356,7 @@ def dense_test_main(args, world, rank, local_rank):
             result["cpu_baseline"] = {"value": round(4 * nb * crops / ct, 2), "unit": "frames/s", "cores": torch.get_num_threads(),
                                       "kind": "port", "sample": "oracle/ssn_oracle.py dense_test_video: %d ticks x %d crops, the "
                                       "reference's batching (4 ticks per call), %.1f s" % (4 * nb, crops, ct)}
+    if rank == 0:
         print(json.dumps(result))
         sys.stdout.flush()
     if world > 1:
@@ -438,8 +468,11 @@ def main():
     seed_one = torch.ones((), device=dev)
     separate_losses = os.environ.get("SSN_BENCH_SEPARATE_LOSSES") == "1"
 
+    last_out = {}       # the heads' outputs of the latest step (--dump-outputs; with a graph: its static output buffers)
+
     def fwd_bwd():
         out = model(*batch)
+        last_out.update(activity_out=out[0].detach(), completeness_out=out[2].detach(), regression_out=out[4].detach())
         if separate_losses:
             loss = (act_crit(out[0], out[1]) + 0.1 * comp_crit(out[2], out[3], 1, 7, global_rows=global_comp_rows)
                     + 0.1 * reg_crit(out[4], out[5], out[6]))
@@ -588,11 +621,19 @@ def main():
         guard["faults"] += 1
         guard["skipped_steps"] += len(guard["pending"])
     rank_ms = 1e3 * elapsed / args.steps
+    if args.dump_outputs and rank == 0:
+        # what a caller of the step receives after the last timed step: its loss and the heads' outputs, and the updated weights and
+        # momentum buffers of every optimised parameter (flattened in optimizer order; DUMP_SAMPLE fixed positions of each)
+        state = [opt.state[p].get("momentum_buffer") for p in params]
+        dump_outputs(args.dump_outputs, dict(
+            last_out, loss=loss.detach().reshape(1),
+            params=torch.cat([p.detach().reshape(-1) for p in params]),
+            momentum=torch.cat([(torch.zeros_like(p) if b is None else b).reshape(-1) for p, b in zip(params, state)])))
 
-    # ---- per-launch HIP events for the roofline: the same K steps once more, launched eagerly (events cannot
+    # ---- --full: per-launch HIP events for the roofline: the same K steps once more, launched eagerly (events cannot
     # be recorded inside a graph replay; the kernels and their arguments are identical)
     prof = None
-    if not args.no_kernel_events and rank == 0:
+    if args.full and not args.no_kernel_events and rank == 0:
         prof = []
         hbm_prof = []
         import action_detection_amd.kernels as K_
@@ -632,8 +673,8 @@ def main():
                 "guard_faults": guard["faults"], "guard_fault_steps": list(guard["fault_polls"]), "redone_steps": guard["redone_steps"]}
         seen = [None] * dist.get_world_size()
         dist.all_gather_object(seen, mine)
-        ar_ms = None
-        if not emulator and reducer is not None:
+        ar_ms = ar_bytes = None
+        if args.full and not emulator and reducer is not None:
             flat = reducer._deferred_flat
             if flat is None:
                 flat = torch.zeros(sum(p.numel() for p in model.base_model.parameters() if p.requires_grad), device=dev)
@@ -646,13 +687,14 @@ def main():
             e1.record()
             torch.cuda.synchronize()
             ar_ms = round(e0.elapsed_time(e1) / 10, 4)
+            ar_bytes = 4 * int(flat.numel())
         try:
             rccl = ".".join(str(x) for x in torch.cuda.nccl.version()) if backend == "nccl" else None
         except Exception:  # noqa: BLE001
             rccl = None
         dist_info = {"ranks_seen": seen, "distinct_devices": len({x["device"] for x in seen}), "rccl_version": rccl,
                      "allreduce_ms_standalone": ar_ms,
-                     "allreduce_bytes": (4 * int(flat.numel()) if (not emulator and reducer is not None) else None)}
+                     "allreduce_bytes": ar_bytes}
 
     proposals = 8 * v * world * args.steps
     value = proposals / elapsed
@@ -822,7 +864,7 @@ def main():
                                      "kernels": out_h}
 
         # ---------------- CPU baseline: the oracle on the host cores, bounded sample ----------------
-        if args.cpu_baseline_videos > 0:
+        if args.full and args.cpu_baseline_videos > 0:
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             import ssn_oracle as O
             cv = args.cpu_baseline_videos
@@ -868,7 +910,7 @@ def main():
         # The headline line above is config 2 (configs[1]); the driver runs this one command, so the other two single-GPU
         # configurations are measured here, each in its own short process (own calibration, own graph, own parity check against the
         # oracle) AFTER the timed region, and reported under `secondary` -- never mixed into `value`.
-        if (world == 1 and not use_dist and not emulator and not args.no_secondary and args.arch == "BNInception"
+        if (args.full and world == 1 and not use_dist and not emulator and not args.no_secondary and args.arch == "BNInception"
                 and args.modality == "RGB" and args.bn_mode == "frozen" and args.precision == "split" and not args.no_graph):
             del oracle_keepalive[:]
             torch.cuda.empty_cache()

@@ -29,6 +29,24 @@ import action_detection_amd  # noqa: E402,F401
 from action_detection_amd.synthetic import init_backbone_synthetic, init_heads_synthetic, make_batch  # noqa: E402
 
 OUT = os.path.join(ROOT, "tests", "golden")
+PART_BYTES = 768 << 10     # compressed bytes per fixture file: a committed file stays under 1 MiB
+
+
+def save_parts(name, out):
+    """np.savez_compressed of `out` as <name>.npz, <name>_2.npz, ...: the arrays in order, a new part whenever the next one would
+    take the current part past PART_BYTES (estimated with zlib).  tests/test_golden.py / test_transforms.py read the parts back as
+    one mapping."""
+    import zlib
+    parts, size = [{}], 0
+    for k, v in out.items():
+        n = len(zlib.compress(np.ascontiguousarray(v).tobytes(), 6))
+        if parts[-1] and size + n > PART_BYTES:
+            parts.append({})
+            size = 0
+        parts[-1][k] = v
+        size += n
+    for i, part in enumerate(parts):
+        np.savez_compressed(os.path.join(OUT, name + ("" if i == 0 else "_%d" % (i + 1)) + ".npz"), **part)
 
 
 def install_shims():
@@ -198,7 +216,7 @@ def golden_ssn(ref_models, ref_ops):
             scores, base = m(frames.reshape(12, -1, size, size), None, None, None, None)
         out["%s_test_scores" % tag] = scores.numpy()
         out["%s_test_base" % tag] = base.numpy()
-    np.savez_compressed(os.path.join(OUT, "ref_ssn.npz"), **out)
+    save_parts("ref_ssn", out)
 
 
 def golden_ssn_bn(ref_models, ref_ops):
@@ -539,7 +557,7 @@ def golden_transforms():
         g = ref_tf.GroupRandomHorizontalFlip(is_flow=False)(msc(imgs))
         out["aug_full_%d" % seed] = np.stack([np.asarray(im) for im in g])
     out["aug_full_boxes"] = np.array(boxes, np.int64)        # (crop_w, crop_h, offset_w, offset_h) per seed
-    np.savez_compressed(os.path.join(OUT, "ref_transforms.npz"), **out)
+    save_parts("ref_transforms", out)
 
 
 def main():

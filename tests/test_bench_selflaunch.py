@@ -61,3 +61,31 @@ def test_bench_self_launch_eight_ranks_with_a_fault_on_rank_5(emu_library, colle
     sg = out["scale_guard"]
     assert sg["scale_overflows"] == 1 and sg["steps_with_skipped_update"] == 3 and sg["steps_redone_eagerly"] == 3
     assert sg["effective_updates"] == out["steps"] + out["warmup"]
+
+
+def test_bench_dump_outputs_are_reproducible(emu_library, tmp_path):
+    """`--dump-outputs DIR`: after the timed steps the loss, the heads' outputs and (a fixed sample of) the updated weights and momentum
+    buffers land in DIR as float32 .npy files, at most 64 MB in all, and two runs with the same arguments write the same arrays."""
+    import numpy as np
+    env = dict(os.environ, SSN_BENCH_EMULATOR="1")
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    dumps = []
+    for run in range(2):
+        d = tmp_path / ("run%d" % run)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--videos-per-gpu", "1",
+               "--frame-size", "16", "--dump-outputs", str(d)]
+        res = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, text=True)
+        assert res.returncode == 0, res.stderr[-2000:]
+        lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, res.stdout
+        out = json.loads(lines[0])
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0
+        files = sorted(os.listdir(d))
+        assert files == sorted(n + ".npy" for n in ("loss", "activity_out", "completeness_out", "regression_out", "params", "momentum"))
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        arrays = {f: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) and a.size > 0 and np.isfinite(a).all() for a in arrays.values())
+        dumps.append(arrays)
+    for f, a in dumps[0].items():
+        np.testing.assert_array_equal(a, dumps[1][f], err_msg=f)

@@ -21,7 +21,13 @@ from test_kernels import rel_err
 
 
 def load(name):
-    return np.load(os.path.join(GOLDEN, name), allow_pickle=False)
+    """A fixture; one that oracle/make_golden.py split into <stem>.npz, <stem>_2.npz, ... (save_parts) is read back whole."""
+    stem = os.path.join(GOLDEN, name[:-len(".npz")])
+    g, k = dict(np.load(stem + ".npz", allow_pickle=False)), 2
+    while os.path.exists("%s_%d.npz" % (stem, k)):
+        g.update(np.load("%s_%d.npz" % (stem, k), allow_pickle=False))
+        k += 1
+    return g
 
 
 # ----------------------------------------------------------------------------- (a) oracle vs reference

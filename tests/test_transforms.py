@@ -18,7 +18,8 @@ import ssn_oracle as O
 from action_detection_amd import transforms as T
 from action_detection_amd.input_pipeline import GpuFrameTransform
 
-G = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_transforms.npz"))
+_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+G = {**np.load(os.path.join(_GOLDEN, "ref_transforms.npz")), **np.load(os.path.join(_GOLDEN, "ref_transforms_2.npz"))}   # (make_golden.py: save_parts)
 CASES = (("over_rgb_roll", "rgb", (24, 24), [104, 117, 128], [1], True),
          ("over_rgb_std", "rgb", (28, 20), [0.485, 0.456, 0.406], [0.229, 0.224, 0.225], False),   # (crop_w, crop_h)
          ("over_flow", "flow", (22, 22), [128], [1], True))

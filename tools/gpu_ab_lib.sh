@@ -8,7 +8,7 @@ cp $L /tmp/new.so
 for rep in ${REPS:-1 2 3}; do
   for which in prev new; do
     if [ $which = prev ]; then cp tools/.ab/libssn_prev.so $L; else cp /tmp/new.so $L; fi
-    timeout 300 python bench.py --cpu-baseline-videos 0 ${BENCH_ARGS:-} > $O/ab_${which}_$rep.json 2> $O/ab_${which}_$rep.err
+    timeout 300 python bench.py --full --cpu-baseline-videos 0 ${BENCH_ARGS:-} > $O/ab_${which}_$rep.json 2> $O/ab_${which}_$rep.err
     python - $O/ab_${which}_$rep.json $which $rep <<'PY'
 import json, sys
 try:

@@ -12,19 +12,19 @@ STAGES=${STAGES:-tests,smoke,bench,flow,dist1,v3,input,prof,pmc,seq,clock,calib}
 R=$(pwd)
 stage_tests() { timeout 3000 python -m pytest tests/ -m gpu -q --durations=15 > $O/gpu_tests.log 2>&1; grep -E "^(FAILED|ERROR)|passed|failed" $O/gpu_tests.log | tail -12; }
 stage_smoke() { timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -1 $O/smoke.log; }
-stage_bench() { timeout 600 python bench.py > $O/bench.json 2> $O/bench.err; cut -c1-300 $O/bench.json; }
-stage_flow() { timeout 600 python bench.py --modality Flow --cpu-baseline-videos 0 > $O/bench_flow.json 2>/dev/null; cut -c1-200 $O/bench_flow.json; }
+stage_bench() { timeout 600 python bench.py --full > $O/bench.json 2> $O/bench.err; cut -c1-300 $O/bench.json; }
+stage_flow() { timeout 600 python bench.py --full --modality Flow --cpu-baseline-videos 0 > $O/bench_flow.json 2>/dev/null; cut -c1-200 $O/bench_flow.json; }
 stage_dist1() {
   for m in separate overlapped; do
-    SSN_FORCE_ALLREDUCE=1 timeout 600 python bench.py --collectives $m --cpu-baseline-videos 0 --no-kernel-events 2> $O/bench_dist1_$m.err | grep '^{' > $O/bench_dist1_$m.json   # (RCCL prints its banner on stdout)
+    SSN_FORCE_ALLREDUCE=1 timeout 600 python bench.py --full --collectives $m --cpu-baseline-videos 0 --no-kernel-events 2> $O/bench_dist1_$m.err | grep '^{' > $O/bench_dist1_$m.json   # (RCCL prints its banner on stdout)
     cut -c1-200 $O/bench_dist1_$m.json; tail -2 $O/bench_dist1_$m.err
   done
 }
 stage_v3() {
-  timeout 900 python bench.py --arch InceptionV3 --videos-per-gpu 2 --steps 5 --warmup 2 --cpu-baseline-videos 0 > $O/bench_train_inceptionv3.json 2> $O/bench_train_inceptionv3.err; cut -c1-300 $O/bench_train_inceptionv3.json; tail -2 $O/bench_train_inceptionv3.err
-  timeout 900 python bench.py --mode dense-test --arch InceptionV3 --steps 3 --warmup 1 > $O/bench_dense_inceptionv3.json 2> $O/bench_dense_inceptionv3.err; cut -c1-300 $O/bench_dense_inceptionv3.json; tail -2 $O/bench_dense_inceptionv3.err
-  SSN_LAYOUT=f32 timeout 900 python bench.py --mode dense-test --arch InceptionV3 --steps 3 --warmup 1 --cpu-baseline-videos 0 > $O/bench_dense_inceptionv3_f32layout.json 2>/dev/null; cut -c1-200 $O/bench_dense_inceptionv3_f32layout.json
-  timeout 900 python bench.py --mode dense-test --steps 3 --warmup 1 --cpu-baseline-videos 0 > $O/bench_dense_bninception.json 2>/dev/null; cut -c1-200 $O/bench_dense_bninception.json
+  timeout 900 python bench.py --full --arch InceptionV3 --videos-per-gpu 2 --steps 5 --warmup 2 --cpu-baseline-videos 0 > $O/bench_train_inceptionv3.json 2> $O/bench_train_inceptionv3.err; cut -c1-300 $O/bench_train_inceptionv3.json; tail -2 $O/bench_train_inceptionv3.err
+  timeout 900 python bench.py --full --mode dense-test --arch InceptionV3 --steps 3 --warmup 1 > $O/bench_dense_inceptionv3.json 2> $O/bench_dense_inceptionv3.err; cut -c1-300 $O/bench_dense_inceptionv3.json; tail -2 $O/bench_dense_inceptionv3.err
+  SSN_LAYOUT=f32 timeout 900 python bench.py --full --mode dense-test --arch InceptionV3 --steps 3 --warmup 1 --cpu-baseline-videos 0 > $O/bench_dense_inceptionv3_f32layout.json 2>/dev/null; cut -c1-200 $O/bench_dense_inceptionv3_f32layout.json
+  timeout 900 python bench.py --full --mode dense-test --steps 3 --warmup 1 --cpu-baseline-videos 0 > $O/bench_dense_bninception.json 2>/dev/null; cut -c1-200 $O/bench_dense_bninception.json
 }
 stage_bnmode() {      # --bn_mode partial: the stem's BatchNorm in training mode, on the planes kernels (1) and on the fp32-layout executor (0)
   for e in 1 0; do

@@ -7,7 +7,7 @@
 O=gpurun_out/r5; mkdir -p $O
 R=$(pwd)
 STAGES=${STAGES:-base,exp,tune,after}
-stage_base() { timeout 400 python bench.py --cpu-baseline-videos 0 > $O/a_bench_base.json 2> $O/a_bench_base.err; cut -c1-400 $O/a_bench_base.json; tail -2 $O/a_bench_base.err; }
+stage_base() { timeout 400 python bench.py --full --cpu-baseline-videos 0 > $O/a_bench_base.json 2> $O/a_bench_base.err; cut -c1-400 $O/a_bench_base.json; tail -2 $O/a_bench_base.err; }
 stage_exp() { SSN_TEST_EXPERIMENTAL=1 timeout 900 python -m pytest tests/test_planes.py -m gpu -q -x --durations=8 > $O/a_exp_tests.log 2>&1; tail -15 $O/a_exp_tests.log; }
 stage_tune() {
   cp action-detection_amd/tuned_tiles_pl.json $O/a_tiles_before.json
@@ -15,5 +15,5 @@ stage_tune() {
   tail -70 $O/a_autotune_splits.txt | cut -c1-230
   cp action-detection_amd/tuned_tiles_pl.json $O/a_tiles_after.json
 }
-stage_after() { timeout 400 python bench.py --cpu-baseline-videos 0 > $O/a_bench_after.json 2> $O/a_bench_after.err; cut -c1-400 $O/a_bench_after.json; tail -2 $O/a_bench_after.err; }
+stage_after() { timeout 400 python bench.py --full --cpu-baseline-videos 0 > $O/a_bench_after.json 2> $O/a_bench_after.err; cut -c1-400 $O/a_bench_after.json; tail -2 $O/a_bench_after.err; }
 for st in ${STAGES//,/ }; do echo "== $st $(date +%T)"; cd $R; stage_$st; done

@@ -19,9 +19,9 @@ stage_ab() {
   for rep in 1 2; do
     for cfg in off default "900,300" "225,75" "1800,600" "450,600" "450,40"; do
       f=$O/b_bench_${cfg//,/_}_$rep.json
-      if [ $cfg = off ]; then SSN_GROUP_WGRAD=0 timeout 300 python bench.py --cpu-baseline-videos 0 > $f 2> $f.err
-      elif [ $cfg = default ]; then timeout 300 python bench.py --cpu-baseline-videos 0 > $f 2> $f.err
-      else SSN_GROUP_TUNING=$cfg timeout 300 python bench.py --cpu-baseline-videos 0 > $f 2> $f.err; fi
+      if [ $cfg = off ]; then SSN_GROUP_WGRAD=0 timeout 300 python bench.py --full --cpu-baseline-videos 0 > $f 2> $f.err
+      elif [ $cfg = default ]; then timeout 300 python bench.py --full --cpu-baseline-videos 0 > $f 2> $f.err
+      else SSN_GROUP_TUNING=$cfg timeout 300 python bench.py --full --cpu-baseline-videos 0 > $f 2> $f.err; fi
       echo "$cfg #$rep"; line $f; grep -v Warning $f.err | grep -i "error\|Traceback" | head -3
     done
   done

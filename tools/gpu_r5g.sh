@@ -6,7 +6,7 @@ timeout 600 python -m pytest tests/test_planes.py -m gpu -q -x -k "wgrad_group o
 timeout 900 python -m pytest tests/test_model_gpu.py -m gpu -q -x -k "fwd_bwd_matches_oracle" 2>&1 | tail -3
 for rep in 1 2 3; do
   for sp in 0 1; do
-    SSN_STEM_PLANES=$sp timeout 300 python bench.py --cpu-baseline-videos 0 > $O/g_bench_stem${sp}_$rep.json 2> $O/g_bench_stem${sp}_$rep.err
+    SSN_STEM_PLANES=$sp timeout 300 python bench.py --full --cpu-baseline-videos 0 > $O/g_bench_stem${sp}_$rep.json 2> $O/g_bench_stem${sp}_$rep.err
     python - $O/g_bench_stem${sp}_$rep.json $sp $rep <<'PY'
 import json, sys
 try:

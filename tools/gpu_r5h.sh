@@ -8,7 +8,7 @@ cp action-detection_amd/tuned_tiles_pl.json $O/tuned_tiles_before.json
 HALO_ONLY=1 KINDS=fwd,dgrad timeout 600 python tools/autotune_pl.py 288 BNInception 2>&1 | tail -40
 cp action-detection_amd/tuned_tiles_pl.json $O/tuned_tiles_after.json
 for r in 1 2; do
-  timeout 300 python bench.py --cpu-baseline-videos 0 > $O/retuned_$r.json 2> $O/retuned_$r.err
+  timeout 300 python bench.py --full --cpu-baseline-videos 0 > $O/retuned_$r.json 2> $O/retuned_$r.err
   python - $O/retuned_$r.json <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])

@@ -8,7 +8,7 @@ timeout 60 python -m pytest tests/test_planes.py -m gpu -x -q -k "wgrad_group" >
 if ! grep -q " passed" $O/k_parity.txt || grep -q "failed\|error" $O/k_parity.txt; then echo "K: PARITY NOT GREEN -> nothing adopted"; exit 0; fi
 echo "K: parity green at ${SECONDS}s"
 cp $L /tmp/new.so
-run() { timeout 60 python bench.py --cpu-baseline-videos 0 > $O/k_$1.json 2> $O/k_$1.err; }
+run() { timeout 60 python bench.py --full --cpu-baseline-videos 0 > $O/k_$1.json 2> $O/k_$1.err; }
 cp tools/.ab/libssn_prev.so $L; run prev
 cp /tmp/new.so $L; run new
 python - $O/k_prev.json $O/k_new.json $SECONDS <<'PY' | tee $O/k_decision.txt

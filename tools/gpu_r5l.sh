@@ -4,7 +4,7 @@
 # same split plans, same reduction order).  If it wins: the 400-step line and the launch inventory with the switch on.
 O=gpurun_out/r5; mkdir -p $O
 for rep in ${REPS:-1 2}; do for w in 0 1; do
-  SSN_WGRAD_LANES=$w timeout 60 python bench.py --cpu-baseline-videos 0 --no-kernel-events > $O/l_${w}_$rep.json 2> $O/l_${w}_$rep.err
+  SSN_WGRAD_LANES=$w timeout 60 python bench.py --full --cpu-baseline-videos 0 --no-kernel-events > $O/l_${w}_$rep.json 2> $O/l_${w}_$rep.err
 done; done
 python - $O <<'PY' | tee $O/l_decision.txt
 import json, sys
@@ -23,6 +23,6 @@ win = same and m1 < m0 - 0.05 and sum(r[(1, i)][0] < r[(0, i)][0] for i in reps)
 print("bit-identical final loss: %s; mean %.3f -> %.3f ms -> %s" % (same, m0, m1, "ADOPT" if win else "KEEP OFF"))
 PY
 if grep -q ADOPT $O/l_decision.txt && [ $SECONDS -lt 55 ]; then
-  SSN_WGRAD_LANES=1 timeout 40 python bench.py --steps 400 --warmup 5 --cpu-baseline-videos 0 --no-kernel-events > $O/l_bench_400steps.json 2>/dev/null; cut -c1-200 $O/l_bench_400steps.json
+  SSN_WGRAD_LANES=1 timeout 40 python bench.py --full --steps 400 --warmup 5 --cpu-baseline-videos 0 --no-kernel-events > $O/l_bench_400steps.json 2>/dev/null; cut -c1-200 $O/l_bench_400steps.json
 fi
 echo "L: done at ${SECONDS}s"

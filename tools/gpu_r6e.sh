@@ -8,7 +8,7 @@ COLD=1 KINDS=fwd,dgrad timeout 1500 python tools/autotune_pl.py 288 BNInception 
 cp $T $O/e_tuned_tiles_pl_cold.json; cp $T /tmp/new_table.json
 for rep in 1 2 3; do for which in old new; do
   cp /tmp/${which}_table.json $T
-  timeout 300 python bench.py --cpu-baseline-videos 0 --no-secondary > $O/e_${which}_$rep.json 2> $O/e_${which}_$rep.err
+  timeout 300 python bench.py --full --cpu-baseline-videos 0 --no-secondary > $O/e_${which}_$rep.json 2> $O/e_${which}_$rep.err
   python - $O/e_${which}_$rep.json $which $rep <<'PY'
 import json, sys
 try:

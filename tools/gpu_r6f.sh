@@ -9,7 +9,7 @@ COLD=1 KINDS=fwd ONLY="|64|7|7|2|224" timeout 600 python tools/autotune_pl.py 28
 cp $T /tmp/new_table.json; cp $T $O/f_tuned_tiles_pl.json
 for rep in 1 2; do for which in old new; do
   cp /tmp/${which}_table.json $T
-  timeout 300 python bench.py --cpu-baseline-videos 0 --no-secondary > $O/f_${which}_$rep.json 2> $O/f_${which}_$rep.err
+  timeout 300 python bench.py --full --cpu-baseline-videos 0 --no-secondary > $O/f_${which}_$rep.json 2> $O/f_${which}_$rep.err
   python - $O/f_${which}_$rep.json $which $rep <<'PY'
 import json, sys
 try:

@@ -4,7 +4,7 @@
 O=gpurun_out/r6; mkdir -p $O
 timeout 600 python -m pytest tests/test_planes.py tests/test_inceptionv3.py -x -q -m gpu -k "stride2 or backbone_backward" > $O/i_tests.txt 2>&1; tail -2 $O/i_tests.txt
 for rep in 1 2 3; do for cfg in "0 0" "1 0" "1 1"; do set -- $cfg
-  SSN_S2_CLASS_LANES=$1 SSN_BENCH_SEPARATE_LOSSES=$2 timeout 300 python bench.py --cpu-baseline-videos 0 --no-secondary > $O/i_$1$2_$rep.json 2> $O/i_$1$2_$rep.err
+  SSN_S2_CLASS_LANES=$1 SSN_BENCH_SEPARATE_LOSSES=$2 timeout 300 python bench.py --full --cpu-baseline-videos 0 --no-secondary > $O/i_$1$2_$rep.json 2> $O/i_$1$2_$rep.err
   python - $O/i_$1$2_$rep.json "classlanes=$1 separate_losses=$2" $rep <<'PY'
 import json, sys
 try:

@@ -8,7 +8,7 @@ COLD=1 KINDS=fwd,dgrad timeout 1800 python tools/autotune_pl.py 288 InceptionV3 
 cp $T /tmp/new_table.json; cp $T $O/o_tuned_tiles_pl.json
 for rep in 1 2; do for which in old new; do
   cp /tmp/${which}_table.json $T
-  timeout 600 python bench.py --mode dense-test --arch InceptionV3 --steps 7 --warmup 1 --proposal-list tests/golden/proposal_list_processed.txt --cpu-baseline-videos 0 > $O/o_dense_${which}_$rep.json 2>/dev/null
+  timeout 600 python bench.py --full --mode dense-test --arch InceptionV3 --steps 7 --warmup 1 --proposal-list tests/golden/proposal_list_processed.txt --cpu-baseline-videos 0 > $O/o_dense_${which}_$rep.json 2>/dev/null
   timeout 600 python bench.py --arch InceptionV3 --videos-per-gpu 2 --steps 5 --warmup 2 --cpu-baseline-videos 0 --no-kernel-events > $O/o_train_${which}_$rep.json 2>/dev/null
   python - $O/o_dense_${which}_$rep.json $O/o_train_${which}_$rep.json $which $rep <<'PY'
 import json, sys

@@ -9,7 +9,7 @@ for mode in 1 0; do
   find $O/r_pmc_$mode -name "*kernel_trace.csv" -delete
 done
 for rep in 1 2 3; do for mode in 0 1; do
-  SSN_WGRAD_GANG=$mode timeout 600 python bench.py --steps 20 --warmup 5 --cpu-baseline-videos 0 --no-secondary > $O/r_${mode}_$rep.json 2> $O/r_${mode}_$rep.err
+  SSN_WGRAD_GANG=$mode timeout 600 python bench.py --full --steps 20 --warmup 5 --cpu-baseline-videos 0 --no-secondary > $O/r_${mode}_$rep.json 2> $O/r_${mode}_$rep.err
   python - $O/r_${mode}_$rep.json $mode $rep <<'PY'
 import json, sys
 try:

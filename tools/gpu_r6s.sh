@@ -5,7 +5,7 @@ for rep in 1 2; do for mode in 0 1; do
   SSN_WGRAD_INTERLEAVE=$mode timeout 600 python tools/pmc_wgrad_alone.py run $O/s_alone_$mode > $O/s_alone_$mode.txt 2> $O/s_alone_$mode.err; echo "interleave=$mode: $(tail -1 $O/s_alone_$mode.txt)"
 done; done
 for rep in 1 2 3; do for mode in 0 1; do
-  SSN_WGRAD_INTERLEAVE=$mode timeout 600 python bench.py --steps 20 --warmup 5 --cpu-baseline-videos 0 --no-secondary > $O/s_${mode}_$rep.json 2> $O/s_${mode}_$rep.err
+  SSN_WGRAD_INTERLEAVE=$mode timeout 600 python bench.py --full --steps 20 --warmup 5 --cpu-baseline-videos 0 --no-secondary > $O/s_${mode}_$rep.json 2> $O/s_${mode}_$rep.err
   python - $O/s_${mode}_$rep.json $mode $rep <<'PY'
 import json, sys
 try:

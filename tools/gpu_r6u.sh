@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; cd "$R"; O=gpurun_out/r6; mkdir -p $O
 timeout 900 python -m pytest tests/test_planes.py -q -x -m gpu -k "pools" 2>&1 | tail -2
 for mode in 0 1 0 1; do SSN_POOL_BANDS=$mode timeout 600 python tools/bench_pool_fwd.py 2>/dev/null | tee -a $O/u_pool_fwd.txt; done
 for rep in 1 2 3; do for mode in 0 1; do
-  SSN_POOL_BANDS=$mode timeout 600 python bench.py --steps 20 --warmup 5 --cpu-baseline-videos 0 --no-secondary > $O/u_${mode}_$rep.json 2> $O/u_err.txt
+  SSN_POOL_BANDS=$mode timeout 600 python bench.py --full --steps 20 --warmup 5 --cpu-baseline-videos 0 --no-secondary > $O/u_${mode}_$rep.json 2> $O/u_err.txt
   python - $O/u_${mode}_$rep.json $mode $rep <<'PY'
 import json, sys
 try:

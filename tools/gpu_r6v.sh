@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd "$R"; O=gpurun_out/r6; mkdir -p $O
 timeout 1500 python -m pytest tests/test_model_gpu.py tests/test_scale_guard.py tests/test_planes.py -q -x -m gpu 2>&1 | tail -3
 for rep in 1 2 3; do for mode in 0 1; do
-  SSN_HEAD_LANES=$mode timeout 600 python bench.py --steps 20 --warmup 5 --cpu-baseline-videos 0 --no-secondary > $O/v_${mode}_$rep.json 2> $O/v_err.txt
+  SSN_HEAD_LANES=$mode timeout 600 python bench.py --full --steps 20 --warmup 5 --cpu-baseline-videos 0 --no-secondary > $O/v_${mode}_$rep.json 2> $O/v_err.txt
   python - $O/v_${mode}_$rep.json $mode $rep <<'PY'
 import json, sys
 try:

@@ -13,7 +13,7 @@ for l in open(sys.argv[1]):
         k = re.sub(r"<.*", "", m.group(2)); tot[k] += float(m.group(1)); n[k] += 1
 print("cap %s: non-conv launches %.1f us: " % (sys.argv[2], sum(tot.values())) + ", ".join("%s %.0f" % (k, v) for k, v in sorted(tot.items(), key=lambda kv: -kv[1])[:12]))
 PY
-  for rep in 1 2 3; do timeout 600 python bench.py --steps 20 --warmup 5 --cpu-baseline-videos 0 --no-secondary 2>/dev/null | python -c "
+  for rep in 1 2 3; do timeout 600 python bench.py --full --steps 20 --warmup 5 --cpu-baseline-videos 0 --no-secondary 2>/dev/null | python -c "
 import json,sys
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('   cap $cap #$rep  %.3f ms/step  loss %.8f' % (d['ms_per_step'], d['final_loss']))"; done
 done 2>&1 | tee $O/w_ab.txt
