@@ -16,8 +16,9 @@
 namespace {
 
 // ---------------------------------------------------------------------------- linear
+// vec: D is a multiple of 4 and x, w are 16-byte aligned (the host checks both), so every row of either starts aligned
 __global__ __launch_bounds__(256) void linear_fwd_kernel(const float* x, const float* w, const float* b, float* out,
-                                                         int R, int O, int D) {
+                                                         int R, int O, int D, int vec) {
     const long wave = ((long)blockIdx.x * 256 + threadIdx.x) >> 6;
     const int lane = threadIdx.x & 63;
     if (wave >= (long)R * O) return;
@@ -25,7 +26,7 @@ __global__ __launch_bounds__(256) void linear_fwd_kernel(const float* x, const f
     const float* xp = x + (long)r * D;
     const float* wp = w + (long)o * D;
     float acc = 0.f;
-    if ((D & 3) == 0) {
+    if (vec) {
         for (int d = lane * 4; d < D; d += 256) {
             const f32x4 xv = *reinterpret_cast<const f32x4*>(xp + d);
             const f32x4 wv = *reinterpret_cast<const f32x4*>(wp + d);
@@ -320,8 +321,11 @@ extern "C" int ssn_linear_fwd(const float* x, const float* w, const float* b, fl
     SSN_CHECK_ARG(x && w && out, "linear_fwd: null pointer");
     if (R == 0 || O == 0) return SSN_OK;
     const long waves = (long)R * O;
+    // 16-byte loads only where every row of both operands starts 16-byte aligned: the shape alone does not say so (a contiguous
+    // view may start anywhere in its storage)
+    const int vec = (D & 3) == 0 && (((uintptr_t)x | (uintptr_t)w) & 15) == 0;
     hipLaunchKernelGGL(linear_fwd_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, x, w, b, out, R, O,
-                       D);
+                       D, vec);
     SSN_CHECK_LAUNCH("linear_fwd");
     return SSN_OK;
 }
@@ -339,8 +343,8 @@ extern "C" int ssn_linear_bwd(const float* dout, const float* x, const float* w,
 
 extern "C" int ssn_row_gather(const float* src, const long* index, float* dst, int n_idx, int width,
                               hipStream_t stream) {
+    if (n_idx == 0) return SSN_OK;      // no row selected: index and dst are empty tensors (no storage), nothing to do
     SSN_CHECK_ARG(src && index && dst, "row_gather: null pointer");
-    if (n_idx == 0) return SSN_OK;
     hipLaunchKernelGGL(row_gather_kernel, dim3((width + 255) / 256, n_idx), dim3(256), 0, stream, src, index, dst,
                        n_idx, width);
     SSN_CHECK_LAUNCH("row_gather");
@@ -349,7 +353,7 @@ extern "C" int ssn_row_gather(const float* src, const long* index, float* dst, i
 // dst[n_rows][width] = 0; dst[index[i]] = src[i]   (indices are unique: they come from nonzero())
 extern "C" int ssn_row_scatter(const float* src, const long* index, float* dst, int n_idx, int n_rows, int width,
                                hipStream_t stream) {
-    SSN_CHECK_ARG(src && index && dst, "row_scatter: null pointer");
+    SSN_CHECK_ARG(dst && (n_idx == 0 || (src && index)), "row_scatter: null pointer");      // (n_idx == 0: src, index empty; dst <- 0)
     const long total = (long)n_rows * width;
     hipLaunchKernelGGL(fill_kernel, dim3(grid_for(total)), dim3(256), 0, stream, dst, total, 0.f);
     if (n_idx)
@@ -505,6 +509,7 @@ struct HeadsArgs {
     float* dw[3];            // backward: weight / bias gradients
     float* db[3];
     int O[3], n[3];
+    int vec[3];              // forward: head h reads its operands with 16-byte loads (D % 4 == 0 and w[h] 16-byte aligned)
     int D, P;
     int wblk0[4];            // backward: first dW block of head h (prefix sums over O_h * chunks_h), [3] = total
     SsnStppTable t;
@@ -561,7 +566,7 @@ __global__ __launch_bounds__(256) void heads_fwd_kernel(HeadsArgs a) {
         {
             const float* wp = a.w[h] + (long)o * Dh;
             float acc = 0.f;
-            if ((Dh & 3) == 0) {
+            if (a.vec[h]) {      // (D, not Dh: the pooled parts start at sh + D, and m * D may be a multiple of 4 where D is not)
                 for (int d = lane * 4; d < Dh; d += 256) {
                     const f32x4 xv = *reinterpret_cast<const f32x4*>(xp + d);
                     const f32x4 wv = *reinterpret_cast<const f32x4*>(wp + d);
@@ -661,7 +666,9 @@ int fill_heads(HeadsArgs& a, const float* ft, const float* scaling, const float*
     SSN_CHECK_ARG(ft && scaling && w && b && pos && idx && out && O && n && act_ft && stpp_ft && table, "%s: null pointer", what);
     SSN_CHECK_ARG(P > 0 && D > 0 && table->n_parts >= 1 && table->n_parts <= SSN_STPP_MAX_PARTS && table->n_seg <= 16,
                   "%s: bad shape (at most 24 parts, 16 segments per proposal)", what);
-    SSN_CHECK_ARG(w[0] && w[1] && pos[0] && pos[1] && out[0] && out[1], "%s: the activity and completeness heads are required", what);
+    // (a head that no proposal selects has an empty output: no storage, n == 0, and nothing reads or writes it)
+    SSN_CHECK_ARG(w[0] && w[1] && pos[0] && pos[1] && (out[0] || n[0] == 0) && (out[1] || n[1] == 0),
+                  "%s: the activity and completeness heads are required", what);
     a.ft = ft;
     a.scaling = scaling;
     for (int h = 0; h < 3; ++h) {
@@ -672,6 +679,7 @@ int fill_heads(HeadsArgs& a, const float* ft, const float* scaling, const float*
         a.out[h] = out[h];
         a.O[h] = O[h];
         a.n[h] = n[h];
+        a.vec[h] = (D & 3) == 0 && ((uintptr_t)w[h] & 15) == 0;
         a.dw[h] = a.db[h] = nullptr;
     }
     a.act_ft = act_ft;

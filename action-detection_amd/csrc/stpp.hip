@@ -132,7 +132,7 @@ __global__ __launch_bounds__(256) void stpp_reorg_kernel(const float* scores, in
 // first runs the folded FC on 10x fewer rows.
 template <bool VEC>
 __global__ __launch_bounds__(256) void crop_mean_kernel(const float* x, float* y, int num_crop, long TD, float inv) {
-    if (VEC) {   // T * D is a multiple of 4: every crop slab starts 16-byte aligned
+    if (VEC) {   // T * D is a multiple of 4 and x, y are 16-byte aligned (the host checks both): every crop slab starts aligned
         const long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
         if (i >= TD) return;
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -147,14 +147,20 @@ __global__ __launch_bounds__(256) void crop_mean_kernel(const float* x, float* y
     }
 }
 // reg [P][C][2] in place: reg[..., k] = reg[..., k] * std[k] + mean[k]   (ssn_test.py:88-90)
+template <bool VEC>      // VEC: reg is 8-byte aligned (the host checks), one 8-byte access per pair
 __global__ __launch_bounds__(256) void reg_denorm_kernel(float* reg, long n_pairs, float mean0, float std0, float mean1,
                                                          float std1) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n_pairs) return;
-    float2 v = *reinterpret_cast<float2*>(reg + 2 * i);
-    v.x = v.x * std0 + mean0;
-    v.y = v.y * std1 + mean1;
-    *reinterpret_cast<float2*>(reg + 2 * i) = v;
+    if (VEC) {
+        float2 v = *reinterpret_cast<float2*>(reg + 2 * i);
+        v.x = v.x * std0 + mean0;
+        v.y = v.y * std1 + mean1;
+        *reinterpret_cast<float2*>(reg + 2 * i) = v;
+    } else {
+        reg[2 * i] = reg[2 * i] * std0 + mean0;
+        reg[2 * i + 1] = reg[2 * i + 1] * std1 + mean1;
+    }
 }
 
 }  // namespace
@@ -165,7 +171,7 @@ extern "C" int ssn_crop_mean(const float* x, float* y, int num_crop, int T, int 
     if (TD == 0) return SSN_OK;      // empty tensors have no storage (NULL) and nothing to do
     SSN_CHECK_ARG(x && y, "crop_mean: null pointer");
     const float inv = 1.0f / (float)num_crop;
-    if (TD % 4 == 0)
+    if (TD % 4 == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0)
         hipLaunchKernelGGL(crop_mean_kernel<true>, dim3((unsigned)((TD / 4 + 255) / 256)), dim3(256), 0, stream, x, y,
                            num_crop, TD, inv);
     else
@@ -180,8 +186,12 @@ extern "C" int ssn_reg_denorm(float* reg, long n_pairs, float mean0, float std0,
     SSN_CHECK_ARG(n_pairs >= 0, "reg_denorm: bad arguments");
     if (n_pairs == 0) return SSN_OK;
     SSN_CHECK_ARG(reg, "reg_denorm: null pointer");
-    hipLaunchKernelGGL(reg_denorm_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, stream, reg, n_pairs,
-                       mean0, std0, mean1, std1);
+    if (((uintptr_t)reg & 7) == 0)
+        hipLaunchKernelGGL(reg_denorm_kernel<true>, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, stream, reg, n_pairs,
+                           mean0, std0, mean1, std1);
+    else
+        hipLaunchKernelGGL(reg_denorm_kernel<false>, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, stream, reg, n_pairs,
+                           mean0, std0, mean1, std1);
     SSN_CHECK_LAUNCH("reg_denorm");
     return SSN_OK;
 }

@@ -987,6 +987,29 @@ def test_stem_space_to_depth(backend):
         assert rel_err(dw, w.grad) < 5e-5 and rel_err(db, b.grad) < 5e-5, (n, c, h)
 
 
+def heads_float64(ft, sc, ws, bs, idx, gouts, part_table, seg_split):
+    """STPP + the three Linear heads + the prop_type row selection restated in float64 torch.  ft [P * n_seg, D], sc [P, 2], ws / bs /
+    idx / gouts: lists of 3 (activity, completeness, regression; None entries = no regression head), part_table: rows of (lo, hi, norm,
+    scale column), seg_split = (x1, x2, n_seg).  Returns the gathered outputs, then the gradients of sum(out * gout) with respect to
+    the features, the weights and the biases (in that order, absent ones left out)."""
+    x1, x2, n_seg = seg_split
+    f64 = ft.double().requires_grad_()
+    w64 = [None if t is None else t.double().requires_grad_() for t in ws]
+    b64 = [None if t is None else t.double().requires_grad_() for t in bs]
+    src = f64.view(ft.shape[0] // n_seg, n_seg, ft.shape[1])
+    parts = []
+    for lo, hi, norm, col in part_table:
+        v = src[:, lo:hi].mean(1) / norm
+        if col >= 0:
+            v = v * sc[:, col:col + 1].double()
+        parts.append(v)
+    act64, st64 = src[:, x1:x2].mean(1), torch.cat(parts, 1)
+    outs64 = [(act64 @ w64[0].t() + b64[0])[idx[0]], (st64 @ w64[1].t() + b64[1])[idx[1]],
+              (st64 @ w64[2].t() + b64[2])[idx[2]] if w64[2] is not None else None]
+    sum((o * go.double()).sum() for o, go in zip(outs64, gouts) if o is not None).backward()
+    return [o for o in outs64 if o is not None] + [t.grad for t in [f64] + w64 + b64 if t is not None]
+
+
 def test_fused_heads_match_the_separate_kernels(backend):
     """functional.HeadsFn (STPP + three Linear heads + prop_type row selection, one launch each way) against the chain of
     StppFn / LinearFn / RowGatherFn it replaces in SSN.train_forward: outputs and every gradient (features, 3 weights, 3 biases),
@@ -1034,20 +1057,6 @@ def test_fused_heads_match_the_separate_kernels(backend):
         for a, b in zip(o1 + g1, o0 + g0):
             assert rel_err(a, b) < 1e-6, (cfg, with_reg, rel_err(a, b))
         # and against float64 torch
-        f64 = ft.double().requires_grad_()
-        w64 = [None if t is None else t.double().requires_grad_() for t in ws]
-        b64 = [None if t is None else t.double().requires_grad_() for t in bs]
-        src = f64.view(p, s, d)
-        parts = []
-        for lo, hi, norm, col in stpp.part_table((2, 7, 9)):
-            v = src[:, lo:hi].mean(1) / norm
-            if col >= 0:
-                v = v * sc[:, col:col + 1].double()
-            parts.append(v)
-        act64, st64 = src[:, 2:7].mean(1), torch.cat(parts, 1)
-        outs64 = [(act64 @ w64[0].t() + b64[0])[idx[0]], (st64 @ w64[1].t() + b64[1])[idx[1]],
-                  (st64 @ w64[2].t() + b64[2])[idx[2]] if with_reg else None]
-        sum((o * go.double()).sum() for o, go in zip(outs64, gouts) if o is not None).backward()
-        ref = [o for o in outs64 if o is not None] + [t.grad for t in [f64] + w64 + b64 if t is not None]
+        ref = heads_float64(ft, sc, ws, bs, idx, gouts, stpp.part_table((2, 7, 9)), (2, 7, 9))
         for a, b in zip(o1 + g1, ref):
             assert rel_err(a, b) < 2e-6, (cfg, with_reg, "float64", rel_err(a, b))
