@@ -806,6 +806,89 @@ def detections(act, comp, reg, rel_prop, top_k, include_bg, nms_thresh, regress)
     return combined, dets, counts
 
 
+def tag_count(scores, h_offsets, d_offsets, thresholds, bw, want_labels=False):
+    """Counting phase of ssn_tag_count for a batch of videos: scores [N, 2] fp32 (the videos one after the other),
+    h_offsets / d_offsets [V + 1] int32 (host / device copy), thresholds [n_thr] fp32 ->
+    (smoothed [N] fp32, labels [n_thr, N] uint8 or None, runs [V, n_thr] int32)."""
+    lib = _check(scores, d_offsets, thresholds)
+    if scores.dim() != 2 or scores.shape[1] != 2 or scores.dtype != torch.float32:
+        raise ValueError("tag_count: scores must be float32 [N, 2], got %s %s" % (scores.dtype, tuple(scores.shape)))
+    if h_offsets.is_cuda or h_offsets.dtype != torch.int32 or d_offsets.dtype != torch.int32 or h_offsets.dim() != 1 \
+            or h_offsets.shape != d_offsets.shape or h_offsets.numel() < 2 or not h_offsets.is_contiguous():
+        raise ValueError("tag_count: offsets must be int32 [V + 1], once on the host and once on the device")
+    if thresholds.dim() != 1 or thresholds.dtype != torch.float32 or thresholds.numel() < 1:
+        raise ValueError("tag_count: thresholds must be float32 [n_thr]")
+    n, v, n_thr = scores.shape[0], h_offsets.numel() - 1, thresholds.numel()
+    dev = scores.device
+    prob = torch.empty(n, device=dev, dtype=torch.float32)
+    smoothed = torch.empty(n, device=dev, dtype=torch.float32)
+    labels = torch.zeros((n_thr, n), device=dev, dtype=torch.uint8) if want_labels else None
+    runs = torch.zeros((v, n_thr), device=dev, dtype=torch.int32)
+    lib.call("ssn_tag_count", _p(scores), h_offsets.data_ptr(), _p(d_offsets), v, n, _p(thresholds), n_thr, float(bw),
+             _p(prob), _p(smoothed), _p(labels), _p(runs), _stream(lib, scores))
+    return smoothed, labels, runs
+
+
+def tag_lds_candidates():
+    return int(_lib.get_lib().cdll.ssn_tag_lds_candidates())
+
+
+def tag_generate(scores, smoothed, d_offsets, durations, thresholds, tolerances, run_off, sort_off, total_runs, sort_entries,
+                 nms_thresh, minimum_len):
+    """Generating phase (ssn_tag_generate).  run_off [V * n_thr + 1] int32 and sort_off [V + 1] int64 on the device, their
+    last entries as total_runs / sort_entries.  -> dict of device tensors indexed like the candidates (cand_box [C, 2],
+    cand_score [C], kept_box [C, 2], kept_score [C], seconds [C, 2], longer [C]) and kept_count [V]."""
+    lib = _check(scores, smoothed, d_offsets, durations, thresholds, tolerances, run_off, sort_off)
+    v, n_thr, n_tol = d_offsets.numel() - 1, thresholds.numel(), tolerances.numel()
+    n = scores.shape[0]
+    if scores.dim() != 2 or scores.shape[1] != 2 or scores.dtype != torch.float32 or smoothed.shape != (n,) \
+            or smoothed.dtype != torch.float32:
+        raise ValueError("tag_generate: scores must be float32 [N, 2] and smoothed float32 [N]")
+    if d_offsets.dim() != 1 or d_offsets.dtype != torch.int32 or v < 1 or thresholds.dim() != 1 \
+            or thresholds.dtype != torch.float32 or tolerances.dim() != 1:
+        raise ValueError("tag_generate: offsets must be int32 [V + 1], thresholds float32 [n_thr], tolerances [n_tol]")
+    if durations.shape != (v,) or durations.dtype != torch.float64 or tolerances.dtype != torch.float64:
+        raise ValueError("tag_generate: durations must be float64 [V] and tolerances float64")
+    if run_off.shape != (v * n_thr + 1,) or run_off.dtype != torch.int32 or sort_off.shape != (v + 1,) \
+            or sort_off.dtype != torch.int64:
+        raise ValueError("tag_generate: run_off must be int32 [V * n_thr + 1] and sort_off int64 [V + 1]")
+    dev = scores.device
+    c = 2 * n_tol * int(total_runs)
+    out = {"cand_box": torch.zeros((c, 2), device=dev, dtype=torch.int32),
+           "cand_score": torch.zeros(c, device=dev, dtype=torch.float32),
+           "kept_box": torch.zeros((c, 2), device=dev, dtype=torch.int32),
+           "kept_score": torch.zeros(c, device=dev, dtype=torch.float32),
+           "seconds": torch.zeros((c, 2), device=dev, dtype=torch.float64),
+           "longer": torch.zeros(c, device=dev, dtype=torch.uint8),
+           "kept_count": torch.zeros(v, device=dev, dtype=torch.int32)}
+    ws_bytes = int(lib.cdll.ssn_tag_workspace_bytes(int(total_runs), int(sort_entries)))
+    ws = torch.zeros((ws_bytes + 3) // 4, device=dev, dtype=torch.int32)
+    lib.call("ssn_tag_generate", _p(scores), _p(smoothed), _p(d_offsets), _p(durations), v, scores.shape[0], _p(thresholds),
+             n_thr, _p(tolerances), n_tol, _p(run_off), _p(sort_off), int(total_runs), int(sort_entries), float(nms_thresh),
+             float(minimum_len), _p(out["cand_box"]), _p(out["cand_score"]), _p(out["kept_box"]), _p(out["kept_score"]),
+             _p(out["seconds"]), _p(out["longer"]), _p(out["kept_count"]), _p(ws), ws_bytes, _stream(lib, scores))
+    return out
+
+
+def tag_name_proposals(gt_span, gt_label, gt_off, prop, prop_off, thresh=0.0):
+    """ssn_tag_name_proposals: gt_span [G, 2] fp64, gt_label [G] int32, gt_off [V + 1] int32, prop [P, 2] fp64, prop_off
+    [V + 1] int32 -> (label [P] int32, iou [P] fp64, overlap_self [P] fp64)."""
+    lib = _check(gt_span, gt_label, gt_off, prop, prop_off)
+    g, p, v = gt_span.shape[0], prop.shape[0], gt_off.numel() - 1
+    if gt_span.shape != (g, 2) or gt_span.dtype != torch.float64 or gt_label.shape != (g,) or gt_label.dtype != torch.int32 \
+            or prop.shape != (p, 2) or prop.dtype != torch.float64 or gt_off.dtype != torch.int32 \
+            or prop_off.dtype != torch.int32 or prop_off.shape != gt_off.shape:
+        raise ValueError("tag_name_proposals: bad shapes / dtypes")
+    dev = prop.device
+    label = torch.zeros(p, device=dev, dtype=torch.int32)
+    iou = torch.zeros(p, device=dev, dtype=torch.float64)
+    own = torch.zeros(p, device=dev, dtype=torch.float64)
+    lib.call("ssn_tag_name_proposals", _p(gt_span) if g else None, _p(gt_label) if g else None, _p(gt_off), g,
+             _p(prop) if p else None, _p(prop_off), v, p, float(thresh), _p(label) if p else None, _p(iou) if p else None,
+             _p(own) if p else None, _stream(lib, prop))
+    return label, iou, own
+
+
 @_hbm_timed
 def linear_fwd(x, w, b, out):
     lib = _check(x, w, b, out)

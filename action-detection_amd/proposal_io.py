@@ -47,6 +47,28 @@ def load_proposal_file(filename):
     return out
 
 
+def format_window_list_record(path, frame_cnt, duration, gt, named_proposals):
+    """One video's record of a proposal list written from spans in SECONDS: the text of the reference's
+    ``dump_window_list`` (/root/reference/ops/io.py:95-134), with the frame count given instead of counted from a frame
+    folder.  gt: ``[(label, (start, end)), ...]`` (label + 1 is written), named_proposals: the tuples of
+    ``tag_proposals.name_proposals``; positions become frame numbers at frame_cnt / duration frames per second."""
+    real_fps = float(frame_cnt) / float(duration)
+    gts = ["{} {} {}".format(g[0] + 1, int(g[1][0] * real_fps), int(g[1][1] * real_fps)) for g in gt]
+    prs = ["{} {:.04f} {:.04f} {} {}".format(p[0], p[1], p[2], int(p[3] * real_fps), int(p[4] * real_fps))
+           for p in named_proposals]
+    return "{}\n{}\n{}\n{}\n{}{}\n{}\n".format(path, frame_cnt, 1, len(gts), "\n".join(gts) + ("\n" if gts else ""),
+                                               len(prs), "\n".join(prs))
+
+
+def write_proposal_file(filename, records):
+    """The records of ``format_window_list_record`` under '# <index>' headers counted from 1, as the reference's
+    proposal scripts write them (gen_bottom_up_proposals.py:188-191); ``load_proposal_file`` reads the file back."""
+    with open(filename, 'w') as f:
+        for i, rec in enumerate(records):
+            f.write('# {}\n'.format(i + 1))
+            f.write(rec)
+
+
 def format_processed_record(idx, frame_path, frame_cnt, gt, prop):
     """One record of a processed list (gt: [label, start, end] ints; prop: [label, iou, overlap_self, start, end])."""
     text = "# {}\n{}\n{}\n1\n{}\n".format(idx, frame_path, frame_cnt, len(gt))

@@ -360,6 +360,42 @@ int ssn_detections(const float* act, const float* comp, const float* reg, const 
                    double* dets, int* counts, void* workspace, size_t ws_bytes, int P, int C, int max_det, int top_k,
                    int include_bg, double nms_thresh, int regress, hipStream_t stream);
 
+/* Temporal actionness grouping for a BATCH of videos (csrc/tag.hip): gen_prop of gen_bottom_up_proposals.py:116-142, i.e.
+ * label_frame_by_threshold (ops/sequence_funcs.py:11-34: fp32 softmax, scipy's gaussian_filter in fp64 with `reflect`
+ * borders, one label row per threshold), build_box_by_search (:101-136), temporal_nms_fallback (:71-97, the `+ 1` form) and
+ * the frames -> seconds conversion with the minimum-length mask (:138-141).  scores [total_T][2] fp32 = the videos'
+ * actionness scores one after the other, offsets [V + 1] int32 frame offsets (given twice: a host copy that is validated
+ * before any launch, and the device copy the kernels read), thresholds [n_thr] fp32, tolerances [n_tol] fp64, durations
+ * [V] fp64 seconds (device).  Two phases with ONE host read between them, whatever V is:
+ *   count:    prob / smoothed [total_T] fp32, labels [n_thr][total_T] uint8 (or NULL), runs [V][n_thr] int32 = foreground
+ *             runs of every label row; the caller forms run_off [V * n_thr + 1] (exclusive prefix sums, int32) and
+ *             sort_off [V + 1] int64 (pow2(candidates) sort entries for every video with more candidates than
+ *             the LDS capacity the library reports, none for the others) and sizes the outputs from them;
+ *   generate: row r emits 2 * n_tol * runs[r] candidates from 2 * n_tol * run_off[r] on, in the reference's order
+ *             (cand_box [C][2] int32, cand_score [C] fp32: sequential fp32 sums, bit-equal to Python's sum()); per video
+ *             the survivors of the NMS from its candidate base on (kept_box, kept_score, seconds [C][2] fp64, longer [C]
+ *             uint8 = span > minimum_len) and kept_count [V].  Equal scores: smaller start, then smaller end, first.
+ * Only the counting phase takes (and validates) a host copy of the offsets; the generating phase follows it on the same
+ * device offsets, and its kernels bound every index they derive from the device tables.  total_T < 2^30.
+ * Non-finite scores are ordered as numpy orders them and can never cause an out-of-range access. */
+int ssn_tag_lds_candidates(void);
+size_t ssn_tag_workspace_bytes(long total_runs, long sort_entries);
+int ssn_tag_count(const float* scores, const int* h_offsets, const int* d_offsets, int V, int total_T,
+                  const float* thresholds, int n_thr, double bw, float* prob, float* smoothed, unsigned char* labels,
+                  int* runs, hipStream_t stream);
+int ssn_tag_generate(const float* scores, const float* smoothed, const int* d_offsets, const double* durations, int V,
+                     int total_T, const float* thresholds, int n_thr, const double* tolerances, int n_tol,
+                     const int* run_off, const long* sort_off, long total_runs, long sort_entries, double nms_thresh,
+                     double minimum_len, int* cand_box, float* cand_score, int* kept_box, float* kept_score,
+                     double* seconds, unsigned char* longer, int* kept_count, void* workspace, size_t ws_bytes,
+                     hipStream_t stream);
+/* name_proposal (ops/detection_metrics.py:54-76) for a batch: ground truth gt_span [G][2] fp64 + gt_label [G] int32 ragged
+ * by gt_off [V + 1], proposals prop [P][2] fp64 ragged by prop_off [V + 1] (all device) -> per proposal the label + 1 of
+ * the instance with the largest temporal IoU (first maximum, IoU > thresh; else 0), that IoU and overlap / own length. */
+int ssn_tag_name_proposals(const double* gt_span, const int* gt_label, const int* gt_off, int G, const double* prop,
+                           const int* prop_off, int V, int P, double thresh, int* out_label, double* out_iou,
+                           double* out_self, hipStream_t stream);
+
 /* ------------------------------------------------------------------ heads
  * nn.Linear fwd/bwd for activity_fc / completeness_fc / regressor_fc / test_fc
  * (ssn_models.py:77-78,87,272-273,283,300; cuBLAS GEMMs in the reference). */
