@@ -24,9 +24,8 @@ class DetectionPostProcessor(object):
         self.cls_top_k = int(cls_top_k)                              # --cls_top_k (default 1, :32)
         self.softmax_before_filter = bool(softmax_before_filter)     # --softmax_before_filter (:28)
 
-    @torch.no_grad()
-    def process_video(self, rel_prop, act_scores, comp_scores, reg_scores=None, device=None, video_cls_score=None):
-        """video_cls_score: the [C] scores of this video from the external classifier's pickle (``--cls_scores``), or None."""
+    def _run(self, rel_prop, act_scores, comp_scores, reg_scores, device, video_cls_score):
+        """-> (combined, dets [C, n_max, 5], counts [C]) on the device and the classes that are reported."""
         dev = torch.device(device) if device is not None else act_scores.device
 
         def f32(t):
@@ -50,6 +49,24 @@ class DetectionPostProcessor(object):
             combined, dets, counts = K.detections(act, comp, reg, rp, self.top_k, self.top_k <= 0, self.nms_threshold,
                                                   not self.no_regression)
             classes = range(self.num_class)
+        return combined, dets, counts, classes
+
+    @torch.no_grad()
+    def process_video(self, rel_prop, act_scores, comp_scores, reg_scores=None, device=None, video_cls_score=None):
+        """video_cls_score: the [C] scores of this video from the external classifier's pickle (``--cls_scores``), or None."""
+        combined, dets, counts, classes = self._run(rel_prop, act_scores, comp_scores, reg_scores, device, video_cls_score)
         counts = counts.cpu().numpy()
         dets = dets.cpu().numpy()
         return {c: dets[c, :counts[c]].copy() for c in classes if counts[c] > 0}, combined
+
+    @torch.no_grad()
+    def process_video_device(self, rel_prop, act_scores, comp_scores, reg_scores=None, device=None, video_cls_score=None):
+        """The same detections WITHOUT the copy to the host: -> ((dets [C, n_max, 5] float64, counts [C] int32), combined),
+        all on the device; class c's rows are ``dets[c, :counts[c]]``.  In the ``--cls_scores`` branch the counts of the
+        classes that are not reported are zero.  ``detection_eval.DetectionEvaluator.add_video`` takes the pair as it is."""
+        combined, dets, counts, classes = self._run(rel_prop, act_scores, comp_scores, reg_scores, device, video_cls_score)
+        if video_cls_score is not None:
+            mask = torch.zeros(self.num_class, dtype=counts.dtype)
+            mask[list(classes)] = 1
+            counts = counts * mask.to(counts.device)
+        return (dets, counts), combined

@@ -889,6 +889,64 @@ def tag_name_proposals(gt_span, gt_label, gt_off, prop, prop_off, thresh=0.0):
     return label, iou, own
 
 
+def eval_lds_gt():
+    return int(_lib.get_lib().cdll.ssn_eval_lds_gt())
+
+
+def eval_count(pred_score, pred_cls, num_class):
+    """ssn_eval_count: pred_score [N] fp64, pred_cls [N] int32 -> counts [C + 1] int32 (device): predictions per class,
+    and in the last entry the rows that cannot be evaluated (class out of range, score not finite)."""
+    lib = _check(pred_score, pred_cls)
+    n = pred_score.shape[0]
+    if pred_score.shape != (n,) or pred_score.dtype != torch.float64 or pred_cls.shape != (n,) or pred_cls.dtype != torch.int32:
+        raise ValueError("eval_count: pred_score must be float64 [N] and pred_cls int32 [N]")
+    counts = torch.zeros(int(num_class) + 1, device=pred_score.device, dtype=torch.int32)
+    lib.call("ssn_eval_count", _p(pred_score) if n else None, _p(pred_cls) if n else None, n, int(num_class), _p(counts),
+             _stream(lib, counts))
+    return counts
+
+
+def eval_ap(pred_seg, pred_score, pred_cls, pred_vid, gt_seg, groups, npos, thresholds, pred_off, sort_off, sort_entries,
+            big_units):
+    """ssn_eval_ap (see include/ssn_hip.h) -> (order [N] int32, tp [T, N] uint8, ap [C, T] fp64), all on the device."""
+    lib = _check(pred_seg, pred_score, pred_cls, pred_vid, gt_seg, groups, npos, thresholds, pred_off, sort_off)
+    n, g, ng, c, t = pred_score.shape[0], gt_seg.shape[0], groups.shape[0], npos.shape[0], thresholds.shape[0]
+    if pred_seg.shape != (n, 2) or pred_seg.dtype != torch.float64 or pred_score.dtype != torch.float64 \
+            or pred_cls.shape != (n,) or pred_cls.dtype != torch.int32 or pred_vid.shape != (n,) or pred_vid.dtype != torch.int32:
+        raise ValueError("eval_ap: predictions must be float64 [N, 2] / [N] and int32 [N] class / video")
+    if gt_seg.shape != (g, 2) or gt_seg.dtype != torch.float64 or groups.shape != (ng, 5) or groups.dtype != torch.int32 \
+            or npos.dtype != torch.int32 or thresholds.dtype != torch.float64 or thresholds.dim() != 1:
+        raise ValueError("eval_ap: ground truth must be float64 [G, 2], int32 [NG, 5] groups and int32 [C] counts")
+    if pred_off.shape != (c + 1,) or pred_off.dtype != torch.int32 or sort_off.shape != (c + 1,) or sort_off.dtype != torch.int64:
+        raise ValueError("eval_ap: pred_off must be int32 [C + 1] and sort_off int64 [C + 1]")
+    dev = thresholds.device
+    order = torch.zeros(n, device=dev, dtype=torch.int32)
+    tp = torch.zeros((t, n), device=dev, dtype=torch.uint8)
+    ap = torch.zeros((c, t), device=dev, dtype=torch.float64)
+    ws_bytes = int(lib.cdll.ssn_eval_workspace_bytes(int(sort_entries), int(big_units), c))
+    ws = torch.zeros((ws_bytes + 7) // 8, device=dev, dtype=torch.int64)
+    lib.call("ssn_eval_ap", _p(pred_seg) if n else None, _p(pred_score) if n else None, _p(pred_cls) if n else None,
+             _p(pred_vid) if n else None, n, _p(gt_seg) if ng else None, _p(groups) if ng else None, ng, g, _p(npos),
+             _p(thresholds), t, c, _p(pred_off), _p(sort_off), int(sort_entries), int(big_units), _p(order) if n else None,
+             _p(tp) if n else None, _p(ap), _p(ws), ws_bytes, _stream(lib, thresholds))
+    return order, tp, ap
+
+
+def eval_recall(gt_span, gt_off, prop, prop_off, thresholds):
+    """ssn_eval_recall: gt_span [G, 2] fp64, gt_off [V + 1] int32, prop [P, 2] fp64, prop_off [V + 1] int32, thresholds [T]
+    fp64 -> hits [V, T] int32."""
+    lib = _check(gt_span, gt_off, prop, prop_off, thresholds)
+    g, p, v, t = gt_span.shape[0], prop.shape[0], gt_off.numel() - 1, thresholds.numel()
+    if gt_span.shape != (g, 2) or gt_span.dtype != torch.float64 or prop.shape != (p, 2) or prop.dtype != torch.float64 \
+            or gt_off.dtype != torch.int32 or prop_off.dtype != torch.int32 or prop_off.shape != gt_off.shape \
+            or thresholds.dtype != torch.float64 or thresholds.dim() != 1 or v < 1:
+        raise ValueError("eval_recall: bad shapes / dtypes")
+    hits = torch.zeros((v, t), device=thresholds.device, dtype=torch.int32)
+    lib.call("ssn_eval_recall", _p(gt_span) if g else None, _p(gt_off), g, _p(prop) if p else None, _p(prop_off), p, v,
+             _p(thresholds), t, _p(hits), _stream(lib, thresholds))
+    return hits
+
+
 @_hbm_timed
 def linear_fwd(x, w, b, out):
     lib = _check(x, w, b, out)

@@ -396,6 +396,34 @@ int ssn_tag_name_proposals(const double* gt_span, const int* gt_label, const int
                            const int* prop_off, int V, int P, double thresh, int* out_label, double* out_iou,
                            double* out_self, hipStream_t stream);
 
+/* Detection evaluation of a whole dataset (csrc/eval.hip): the stage of eval_detection_results.py between ravel_detections
+ * (:188) and the mean over classes (:237).  The AP function the reference calls there (:14, :220) belongs to the ActivityNet
+ * toolkit, a submodule that is empty in the reference tree; the algorithm is restated in DESIGN.md.  Predictions of all
+ * classes and videos flat in any order: pred_seg [N][2], pred_score [N] fp64, pred_cls / pred_vid [N] int32.  Ground truth
+ * (get_all_gt, :200-203): gt_seg [G][2] fp64 with the rows of one (class, video) group next to each other in their input
+ * order, groups [NG][5] int32 = (class, video, first row, rows, offset of the group's scratch in 8-byte units), npos [C]
+ * int32 rows per class.  thresholds [T] fp64 (:209-212), T <= 32.  Two phases with ONE host read between them:
+ *   count: counts [C + 1] int32 = predictions per class, counts[C] = rows with a class outside [0, C) or a score that is
+ *          not finite (the caller refuses those); the caller forms pred_off [C + 1] int32 (exclusive prefix sums) and
+ *          sort_off [C + 1] int64 (the same with every class rounded up to a power of two, 0 stays 0);
+ *   ap:    order [N] int32 = flat indices class by class in descending score, equal scores lower flat index first; tp
+ *          [T][N] uint8 in that order; ap [C][T] fp64, NaN for a class without ground truth.  Among ground-truth rows of
+ *          equal IoU the earlier row is matched.  IoU = inter / ((ge - gs) + (e - s) - inter) in fp64, in that order.
+ * A group with more rows than the LDS capacity the library reports takes rows + 32 * ceil(rows / 64) units of scratch
+ * (`big_units` in total).  The kernels bound every index they derive from the device tables. */
+int ssn_eval_lds_gt(void);
+size_t ssn_eval_workspace_bytes(long sort_entries, long big_units, int C);
+int ssn_eval_count(const double* pred_score, const int* pred_cls, int N, int C, int* counts, hipStream_t stream);
+int ssn_eval_ap(const double* pred_seg, const double* pred_score, const int* pred_cls, const int* pred_vid, int N,
+                const double* gt_seg, const int* groups, int NG, int G, const int* npos, const double* thresholds, int T, int C,
+                const int* pred_off, const long* sort_off, long sort_entries, long big_units, int* order, unsigned char* tp,
+                double* ap, void* workspace, size_t ws_bytes, hipStream_t stream);
+/* temporal_recall (ops/detection_metrics.py:31-51, with temporal_iou :7-20: intersection over the hull) for a batch: gt_span
+ * [G][2] fp64 ragged by gt_off [V + 1], prop [P][2] fp64 ragged by prop_off [V + 1], thresholds [T] fp64 (all device) -> hits
+ * [V][T] int32: ground-truth spans of video v that some proposal overlaps with an IoU strictly above threshold t. */
+int ssn_eval_recall(const double* gt_span, const int* gt_off, int G, const double* prop, const int* prop_off, int P, int V,
+                    const double* thresholds, int T, int* hits, hipStream_t stream);
+
 /* ------------------------------------------------------------------ heads
  * nn.Linear fwd/bwd for activity_fc / completeness_fc / regressor_fc / test_fc
  * (ssn_models.py:77-78,87,272-273,283,300; cuBLAS GEMMs in the reference). */
