@@ -19,7 +19,7 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(_HERE, "libssn_hip.so")
-SOURCES = ["conv_igemm.hip", "conv_x6.hip", "conv_x6_rect.hip", "conv_wgrad.hip", "conv_wgrad_x6.hip", "elementwise.hip", "bn_train.hip", "frames.hip", "detect.hip", "pool.hip", "stpp.hip", "heads_losses.hip", "conv_pl.hip", "planes_ops.hip", "planes_bn.hip", "wgrad_pl.hip", "tag.hip", "eval.hip"]
+SOURCES = ["conv_igemm.hip", "conv_x6.hip", "conv_x6_rect.hip", "conv_wgrad.hip", "conv_wgrad_x6.hip", "elementwise.hip", "bn_train.hip", "frames.hip", "detect.hip", "pool.hip", "stpp.hip", "heads_losses.hip", "conv_pl.hip", "planes_ops.hip", "planes_bn.hip", "wgrad_pl.hip", "tag.hip", "eval.hip", "actionness.hip"]
 
 STPP_MAX_PARTS = 24
 
@@ -79,6 +79,9 @@ _SIGS = {
     "ssn_eval_count": "ppiipp",
     "ssn_eval_ap": "ppppippiippiippllpppplp",
     "ssn_eval_recall": "ppippiipipp",
+    "ssn_actionness_fc": "ppppiiiiiip",
+    "ssn_actionness_group": "pppiiiip",
+    "ssn_actionness_merge": "pppppiiiiip",
     "ssn_frames_crop_normalize": "ppiiiiiiipppiipipip",
     "ssn_frames_crop_resize_normalize": "ppiiiiiippiipipipup",
     "ssn_reg_denorm": "plffffp",

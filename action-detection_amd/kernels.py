@@ -947,6 +947,59 @@ def eval_recall(gt_span, gt_off, prop, prop_off, thresholds):
     return hits
 
 
+def actionness_fc(feat, w, b, raw_true, tick0, num_crop):
+    """ssn_actionness_fc: feat [num_crop * ticks, D] (crop-major backbone output of one call), w [C, D], b [C] or None ->
+    raw_true[tick0 + t, c, :] = logits of feature row c * ticks + t; raw_true [T, num_crop, C] is the video's staging tensor."""
+    lib = _check(feat, w, b, raw_true)
+    if feat.dim() != 2 or w.dim() != 2 or feat.shape[1] != w.shape[1] or feat.dtype != torch.float32 or w.dtype != torch.float32:
+        raise ValueError("actionness_fc: feat must be float32 [R, D] and w float32 [C, D]")
+    c, d = w.shape
+    if raw_true.dim() != 3 or raw_true.shape[1] != num_crop or raw_true.shape[2] != c or raw_true.dtype != torch.float32:
+        raise ValueError("actionness_fc: raw_true must be float32 [T, %d, %d], got %s" % (num_crop, c, tuple(raw_true.shape)))
+    if feat.shape[0] % num_crop or (b is not None and (b.shape != (c,) or b.dtype != torch.float32)):
+        raise ValueError("actionness_fc: %d feature rows are not a multiple of %d crops, or bad bias" % (feat.shape[0], num_crop))
+    ticks = feat.shape[0] // num_crop
+    lib.call("ssn_actionness_fc", _p(feat) if ticks else None, _p(w), _p(b), _p(raw_true) if ticks else None, ticks,
+             int(num_crop), c, d, int(tick0), raw_true.shape[0], _stream(lib, raw_true))
+
+
+def actionness_group(raw_true, ref_batch, raw=None):
+    """ssn_actionness_group: raw_true [T, crops, C] -> (raw [T, crops, C], mean [T, C]).  ref_batch 0: raw is raw_true
+    (no copy unless `raw` is given); ref_batch g > 0: the rows binary_test.py writes with g ticks per generator batch."""
+    lib = _check(raw_true, raw)
+    if raw_true.dim() != 3 or raw_true.dtype != torch.float32 or raw_true.shape[1] < 1 or raw_true.shape[2] < 1:
+        raise ValueError("actionness_group: raw_true must be float32 [T, crops >= 1, C >= 1]")
+    t, crops, c = raw_true.shape
+    if raw is None:
+        raw = raw_true if int(ref_batch) == 0 else torch.empty_like(raw_true)
+    if raw.shape != raw_true.shape or raw.dtype != torch.float32:
+        raise ValueError("actionness_group: raw must be float32 %s" % (tuple(raw_true.shape),))
+    mean = torch.empty((t, c), device=raw_true.device, dtype=torch.float32)
+    lib.call("ssn_actionness_group", _p(raw_true) if t else None, _p(raw) if t else None, _p(mean) if t else None, t, crops, c,
+             int(ref_batch), _stream(lib, raw_true))
+    return raw, mean
+
+
+def actionness_merge(rows, offsets, weights, out_offsets, out_rows, out=None):
+    """ssn_actionness_merge: rows [N, C] fp32 (stream-major), offsets [S * V + 1] int32, weights [S] fp32, out_offsets
+    [V + 1] int32, all on the device -> out [out_rows, C] (zeros where the tables of a video are inconsistent)."""
+    lib = _check(rows, offsets, weights, out_offsets, out)
+    s, v = weights.numel(), out_offsets.numel() - 1
+    if rows.dim() != 2 or rows.dtype != torch.float32 or weights.dtype != torch.float32 or weights.dim() != 1 or s < 1:
+        raise ValueError("actionness_merge: rows must be float32 [N, C] and weights float32 [S]")
+    if offsets.dtype != torch.int32 or out_offsets.dtype != torch.int32 or v < 1 or offsets.shape != (s * v + 1,) \
+            or out_offsets.dim() != 1:
+        raise ValueError("actionness_merge: offsets must be int32 [S * V + 1] and out_offsets int32 [V + 1]")
+    c = rows.shape[1]
+    if out is None:
+        out = torch.zeros((int(out_rows), c), device=rows.device, dtype=torch.float32)
+    if out.shape != (int(out_rows), c) or out.dtype != torch.float32:
+        raise ValueError("actionness_merge: out must be float32 [%d, %d]" % (int(out_rows), c))
+    lib.call("ssn_actionness_merge", _p(rows) if rows.shape[0] else None, _p(offsets), _p(weights), _p(out_offsets),
+             _p(out) if out_rows else None, s, v, c, rows.shape[0], int(out_rows), _stream(lib, rows))
+    return out
+
+
 @_hbm_timed
 def linear_fwd(x, w, b, out):
     lib = _check(x, w, b, out)

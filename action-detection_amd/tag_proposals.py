@@ -61,6 +61,47 @@ def merge_scores(score_dicts, weights=None):
     return out
 
 
+@torch.no_grad()
+def merge_scores_device(streams, weights=None):
+    """``merge_scores`` without leaving the GPU: ``streams`` is a list of ``{video id: float32 [T_s, C] device tensor}``,
+    already crop-averaged (``ActionnessScores.mean``); -> ``{video id: [T, C] device tensor}`` from ONE
+    ``ssn_actionness_merge`` launch for all videos.  Same arithmetic, bit for bit: weights rounded to float32, multiply then
+    add, a shorter stream truncates the sum, a longer one is read at ``int(x * (T_s / float(T)))``.  The output lengths
+    follow from the input lengths, so nothing is read back."""
+    if len(streams) < 1:
+        raise ValueError("merge_scores_device: at least one stream")
+    if weights is not None and len(weights) != len(streams):
+        raise ValueError("merge_scores_device: one weight per stream")
+    keys = list(streams[0])
+    if not keys:
+        return {}
+    parts, lens = [], []
+    for st in streams:
+        for k in keys:
+            t = st[k]
+            if not torch.is_tensor(t) or t.dim() != 2 or t.dtype != torch.float32 or t.shape[0] < 1 \
+                    or t.shape[1] != streams[0][keys[0]].shape[1]:
+                raise ValueError("merge_scores_device: every stream must hold float32 [T >= 1, C] tensors, got %r for %r"
+                                 % (getattr(t, "shape", t), k))
+            parts.append(t)
+            lens.append(t.shape[0])
+    dev = parts[0].device
+    v = len(keys)
+    lens = np.asarray(lens, dtype=np.int64).reshape(len(streams), v)
+    out_len = lens[0].copy()
+    for s in range(1, len(streams)):            # (a longer stream is resampled: the merged length only ever shrinks)
+        out_len = np.minimum(out_len, lens[s])
+    off = np.concatenate([[0], np.cumsum(lens.ravel())])
+    out_off = np.concatenate([[0], np.cumsum(out_len)])
+    if off[-1] >= 2 ** 30:
+        raise ValueError("merge_scores_device: more than 2^30 rows in one batch")
+    w = np.asarray([1.0 if weights is None else weights[i] for i in range(len(streams))], dtype=np.float32)
+    rows = torch.cat([p.to(dev) for p in parts]).contiguous()
+    out = K.actionness_merge(rows, torch.from_numpy(off.astype(np.int32)).to(dev), torch.from_numpy(w).to(dev),
+                             torch.from_numpy(out_off.astype(np.int32)).to(dev), int(out_off[-1]))
+    return {k: out[int(out_off[i]):int(out_off[i + 1])] for i, k in enumerate(keys)}
+
+
 def sliding_window_proposals(duration, time_step=1, max_level=8, overlap=0.4):
     """Exponential sliding windows over a video of ``duration`` seconds (ops/sequence_funcs.py:37-54): spans of
     2**level seconds every ceil(span * (1 - overlap)), kept when at least one second lies inside the video."""

@@ -424,6 +424,29 @@ int ssn_eval_ap(const double* pred_seg, const double* pred_score, const int* pre
 int ssn_eval_recall(const double* gt_span, const int* gt_off, int G, const double* prop, const int* prop_off, int P, int V,
                     const double* thresholds, int T, int* hits, hipStream_t stream);
 
+/* The scoring tail of the actionness stage and the merge in front of TAG (csrc/actionness.hip).
+ * fc: test_fc on the backbone output of one call (binary_test.py:89, binary_model.py:237-240; a cuBLAS GEMM in the reference).
+ *   feat [num_crop * ticks][D] fp32 crop-major, w [C][D], b [C] or NULL -> raw_true [T][num_crop][C], the video's staging
+ *   tensor in TRUE layout: the logits of feature row c * ticks + t go to raw_true[tick0 + t][c][:].  One wave per row,
+ *   16-byte loads, a summation order that depends on D alone (a tick scores bit-identically in any batching); any C, any D.
+ * group: binary_test.py:84,90-92 for one video.  ref_batch 0: raw = raw_true (raw may be the same buffer).  ref_batch g > 0:
+ *   the rows the reference writes, whose view(-1, num_crop, D) reads a crop-major batch of g ticks (load_binary_score.py:265)
+ *   as tick-major: with q = i / g, b = min(g, T - g q), r = (i - g q) * num_crop + j, raw[i][j] = raw_true[g q + r % b][r / b].
+ *   mean [T][C] = the crop mean of raw as gen_bottom_up_proposals.py:78 takes it: slot 0, plus slots 1 .. num_crop - 1 in
+ *   order, one division by float(num_crop); bit-equal to numpy's.
+ * merge: the merging loop of gen_bottom_up_proposals.py:76-91 for V videos x S streams in one launch.  rows [total_rows][C]
+ *   fp32 = the crop-averaged scores stream-major (stream s of video v: rows offsets[s * V + v] .. offsets[s * V + v + 1]),
+ *   offsets [S * V + 1] int32, weights [S] fp32, out_offsets [V + 1] int32 (all device), out [out_rows][C].  A shorter stream
+ *   truncates the sum (for the streams after it too), a longer one is read at int(x * (T_add / float(T))) in fp64; fp32
+ *   multiply, then add.  The output lengths follow from the input lengths, which the caller knows.  Every index derived from
+ *   the device tables is bounded against total_rows / out_rows: a video whose tables are inconsistent writes nothing. */
+int ssn_actionness_fc(const float* feat, const float* w, const float* b, float* raw_true, int ticks, int num_crop, int C, int D,
+                      int tick0, int T, hipStream_t stream);
+int ssn_actionness_group(const float* raw_true, float* raw, float* mean, int T, int num_crop, int C, int ref_batch,
+                         hipStream_t stream);
+int ssn_actionness_merge(const float* rows, const int* offsets, const float* weights, const int* out_offsets, float* out, int S,
+                         int V, int C, int total_rows, int out_rows, hipStream_t stream);
+
 /* ------------------------------------------------------------------ heads
  * nn.Linear fwd/bwd for activity_fc / completeness_fc / regressor_fc / test_fc
  * (ssn_models.py:77-78,87,272-273,283,300; cuBLAS GEMMs in the reference). */

@@ -1,0 +1,116 @@
+#!/usr/bin/env python
+"""Extract actionness scores: the counterpart of the reference's binary_test.py on the kernels of this project.
+
+A trained ``BinaryClassifier`` runs over every ``--frame_interval``-th frame of every video of a proposal list and the
+``{video id: float32 [T, crops, 2]}`` score file ``gen_bottom_up_proposals.py`` (here: ``tag_proposals``) reads is written.
+Flags are named as the reference's; ``--proposal-list`` stands in for its YAML lookup of (dataset, subset), ``--frame-root`` for
+the frame folders the list names.  ``--grouping reference`` (default) writes exactly the rows binary_test.py writes, ``tick``
+the honest ones (actionness_test.py says what the difference is).
+
+    python tools/extract_actionness.py RGB weights.pth.tar scores_rgb.pc --proposal-list data/thumos14_tag_val_proposal_list.txt \\
+        --frame-root /data/frames --frame_interval 5 --test_crops 10
+
+The frame source is a callable ``load(video id, frame number) -> [PIL images]`` (one RGB image, or the x and y flow images);
+``pil_loader`` below reads the reference's file layout.  ``extract(...)`` takes any other.
+"""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def pil_loader(frame_root, modality, flow_pref=""):
+    """load_binary_score.py:198-205: img_{:05d}.jpg, or {flow_pref}x_{:05d}.jpg + {flow_pref}y_{:05d}.jpg as 'L' images."""
+    from PIL import Image
+
+    def load(vid, idx):
+        folder = os.path.join(frame_root, vid)
+        if modality == "RGB":
+            return [Image.open(os.path.join(folder, "img_{:05d}.jpg".format(idx))).convert("RGB")]
+        return [Image.open(os.path.join(folder, "{}{}_{:05d}.jpg".format(flow_pref, p, idx))).convert("L") for p in "xy"]
+    return load
+
+
+def frame_batches(load, video, sampler, transform, gen_batch=4):
+    """The generator of load_binary_score.get_test_data (:288-304): gen_batch ticks per batch, crop-major after the transform."""
+    frames = []
+    for n, row in enumerate(sampler.test_frames(video)):
+        for idx in row:
+            frames.extend(load(video.id, int(idx)))
+        if (n + 1) % gen_batch == 0:
+            yield transform(frames)
+            frames = []
+    if frames:
+        yield transform(frames)
+
+
+def extract(net, sampler, load, test_crops=10, input_size=None, tick_batch=32, grouping="reference", max_num=-1, verbose=True):
+    """-> ActionnessScores of the first max_num (all) videos of the sampler's list; ``net`` as ActionnessTester takes it."""
+    import time
+    from action_detection_amd import transforms as T
+    from action_detection_amd.actionness_test import ActionnessTester
+    input_size = net.input_size if input_size is None else input_size
+    if test_crops == 1:
+        cropping = [T.GroupScale(net.scale_size), T.GroupScale(input_size)]
+    elif test_crops == 10:
+        cropping = [T.GroupOverSample(input_size, net.scale_size)]
+    else:
+        raise ValueError("only 1 and 10 crops are supported while we got {}".format(test_crops))
+    transform = T.Compose(cropping + [T.Stack(roll=True), T.ToTorchFormatTensor(div=False),
+                                      T.GroupNormalize(net.input_mean, net.input_std)])
+    tester = ActionnessTester(net, tick_batch=tick_batch, grouping=grouping)
+    videos = sampler.video_list if max_num <= 0 else sampler.video_list[:max_num]
+    start = time.time()
+
+    def items():
+        for i, video in enumerate(videos):
+            yield video.id.split('/')[-1], frame_batches(load, video, sampler, transform), len(sampler.test_ticks(video)), test_crops
+            if verbose and i:
+                print('video {} done, total {}/{}, average {:.04f} sec/video'.format(i - 1, i, len(videos),
+                                                                                     (time.time() - start) / i))
+    return tester.score_videos(items())
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="extract actionness scores")
+    ap.add_argument("modality", type=str, choices=["RGB", "Flow"])
+    ap.add_argument("weights", type=str)
+    ap.add_argument("save_scores", type=str)
+    ap.add_argument("--proposal-list", required=True, help="the processed proposal list of the subset to score")
+    ap.add_argument("--frame-root", type=str, default="")
+    ap.add_argument("--arch", type=str, default="BNInception", choices=["BNInception", "InceptionV3"])
+    ap.add_argument("--frame_interval", type=int, default=5)
+    ap.add_argument("--max_num", type=int, default=-1)
+    ap.add_argument("--test_crops", type=int, default=10)
+    ap.add_argument("--input_size", type=int, default=None)
+    ap.add_argument("--flow_pref", type=str, default="")
+    ap.add_argument("--tick_batch", type=int, default=32)
+    ap.add_argument("--grouping", type=str, default="reference", choices=["reference", "tick"])
+    ap.add_argument("--device", type=str, default="cuda:0")
+    args = ap.parse_args(argv)
+
+    import torch
+    import action_detection_amd as pkg
+    from action_detection_amd.actionness_sampling import ActionnessSampler
+    from action_detection_amd.binary_model import BinaryClassifier
+    pkg.build()
+    data_length = 1 if args.modality == "RGB" else 5
+    net = BinaryClassifier(2, 5, args.modality, test_mode=True, new_length=data_length, base_model=args.arch)
+    checkpoint = torch.load(args.weights, map_location="cpu")
+    print("model epoch {} loss: {}".format(checkpoint.get('epoch'), checkpoint.get('best_loss')))
+    net.load_state_dict({'.'.join(k.split('.')[1:]): v for k, v in checkpoint['state_dict'].items()})
+    net.prepare_test_fc()
+    net.to(args.device).eval()
+    sampler = ActionnessSampler(args.proposal_list, new_length=data_length, test_interval=args.frame_interval)
+    scores = extract(net, sampler, pil_loader(args.frame_root, args.modality, args.flow_pref), args.test_crops, args.input_size,
+                     args.tick_batch, args.grouping, args.max_num)
+    scores.save(args.save_scores)
+    print("wrote {} videos to {}".format(len(scores), args.save_scores))
+    return scores
+
+
+if __name__ == "__main__":
+    main()
