@@ -1165,6 +1165,80 @@ def sgd_step_multi(ws, grads, bufs, lrs, wds, momentum, grad_scale=1.0, first_st
              int(first_step), _p(skip_flag), _stream(lib, ws[0]))
 
 
+def sgd_step_multi_dev(ws, grads, bufs, lrs, wds, momentum, grad_scale_dev, first_step=False, skip_flag=None):
+    """sgd_step_multi with the gradient scale read from the device: grad_scale_dev is a fp32 tensor whose first element is the
+    scale (``sumsq_multi(...)[1:]``).  Same update, same launches, nothing read by the host."""
+    if not ws:
+        return
+    global PARAM_EPOCH
+    PARAM_EPOCH += 1
+    lib = _check(*ws, *grads, *bufs, grad_scale_dev)
+    n = len(ws)
+    sizes = (ctypes.c_long * n)(*[w.numel() for w in ws])
+    lr = (ctypes.c_float * n)(*[float(v) for v in lrs])
+    wd = (ctypes.c_float * n)(*[float(v) for v in wds])
+    pw, pg, pb = _ptr_array(ws), _ptr_array(grads), _ptr_array(bufs)   # keep the arrays alive across the call
+    lib.call("ssn_sgd_step_multi_dev", n, ctypes.addressof(pw), ctypes.addressof(pg), ctypes.addressof(pb),
+             ctypes.addressof(sizes), ctypes.addressof(lr), ctypes.addressof(wd), float(momentum), _p(grad_scale_dev),
+             int(first_step), _p(skip_flag), _stream(lib, ws[0]))
+
+
+def sumsq_multi_workspace_floats(sizes):
+    lib = _lib.get_lib()
+    n = len(sizes)
+    arr = (ctypes.c_long * max(n, 1))(*[int(v) for v in sizes])
+    return int(lib.cdll.ssn_sumsq_multi_workspace_floats(n, ctypes.addressof(arr)))
+
+
+def sumsq_multi(xs, pre_scale=1.0, max_norm=0.0, out=None, workspace=None):
+    """2-norm over the fp32 tensors ``xs`` (contiguous, any 4-byte alignment, empty ones allowed) in ceil(len / 48) + 1 launches,
+    deterministic.  Returns the device tensor ``out`` [2]: out[0] = norm * pre_scale, out[1] = the gradient scale of
+    /root/reference/ssn_train.py:239-248 (pre_scale, times max_norm / (out[0] + 1e-6) when that is below 1; max_norm <= 0: no
+    clipping).  No host read; nothing is allocated when ``out`` and ``workspace`` (>= sumsq_multi_workspace_floats) are given."""
+    if not xs:
+        raise ValueError("sumsq_multi needs at least one tensor")
+    lib = _check(*xs, out, workspace)
+    n = len(xs)
+    sizes = (ctypes.c_long * n)(*[x.numel() for x in xs])
+    if workspace is None:
+        workspace = torch.empty(int(lib.cdll.ssn_sumsq_multi_workspace_floats(n, ctypes.addressof(sizes))), device=xs[0].device,
+                                dtype=torch.float32)
+    if out is None:
+        out = torch.empty(2, device=xs[0].device, dtype=torch.float32)
+    if out.dtype != torch.float32 or out.numel() < 2 or workspace.dtype != torch.float32:
+        raise ValueError("sumsq_multi: out must be fp32 [2], workspace fp32")
+    px = _ptr_array(xs)      # kept alive across the call
+    lib.call("ssn_sumsq_multi", n, ctypes.addressof(px), ctypes.addressof(sizes), _p(workspace), workspace.numel(),
+             float(pre_scale), float(max_norm), _p(out), _stream(lib, xs[0]))
+    return out
+
+
+def step_meters(logits, target, losses, loss_weight, state, skip_flag=None):
+    """AverageMeter.update of every meter of one training / validation step in one launch (csrc/train_step.hip).  logits fp32
+    [rows, cols] (rows may be strided), target int64 [rows], losses fp32 [n_losses <= 4] or None, state float64
+    [(n_losses + 3) * 4 + 1] updated in place."""
+    if logits.dim() != 2 or logits.stride(1) != 1 or logits.dtype != torch.float32:
+        raise ValueError("step_meters: logits must be fp32 [rows, cols] with unit column stride")
+    if target.dtype != torch.int64 or target.numel() != logits.shape[0] or not target.is_contiguous():
+        raise ValueError("step_meters: target must be contiguous int64 [rows]")
+    n_losses = 0 if losses is None else losses.numel()
+    if losses is not None and losses.dtype != torch.float32:
+        raise ValueError("step_meters: losses must be fp32")
+    if state.dtype != torch.float64 or state.numel() != (n_losses + 3) * 4 + 1:
+        raise ValueError("step_meters: state must be float64 [(n_losses + 3) * 4 + 1]")
+    lib = _check(target, losses, state, skip_flag)
+    if not lib.is_emulator and not logits.is_cuda:
+        raise RuntimeError("SSN HIP ops need HIP (cuda) tensors; there is no CPU fallback")
+    rows, cols = logits.shape
+    lib.call("ssn_step_meters", _p(logits), logits.stride(0) if rows > 1 else cols, _p(target), rows, cols, _p(losses), n_losses,
+             float(loss_weight), _p(state), _p(skip_flag), _stream(lib, logits))
+
+
+def train_step_launches(reset=False):
+    """Kernel launches issued by step_meters / sumsq_multi / sgd_step_multi_dev on this thread since the last reset."""
+    return int(_lib.get_lib().cdll.ssn_train_step_launches(1 if reset else 0))
+
+
 def wgrad_reduce(part, dw, db, splits, taps=1):
     """dw [M, K] (any trailing shape), db [M] or None <- sum over the `splits` partial slabs part [splits, M, K + 1] in a fixed
     order (column K = bias).  taps > 1: the slabs' columns are tap-major (column t * (K / taps) + ci holds dW[m][ci][t]), the

@@ -34,11 +34,12 @@ class SSNSGD(torch.optim.Optimizer):
             g["weight_decay"] = self.base_wd * g["decay_mult"]
 
     @torch.no_grad()
-    def step(self, closure=None, grad_scale=1.0, skip_flag=None):
+    def step(self, closure=None, grad_scale=1.0, skip_flag=None, grad_scale_dev=None):
         """All parameter tensors in ceil(#tensors / 48) fused launches (ssn_sgd_step_multi).  skip_flag: device int32 tensor
         (``SSN.scale_fault_flag()``); while its first word is non-zero the launches leave weights and momentum untouched -- the
         range guard of the planes path flagged this step's gradients, the step is to be repeated (needed where the host cannot
-        look before the update runs: inside a hipGraph replay)."""
+        look before the update runs: inside a hipGraph replay).  grad_scale_dev: device fp32 tensor whose first element is the gradient
+        scale (``clip_grad_norm_device(...)[1:]``); replaces grad_scale, same update bit for bit, nothing read by the host."""
         batches = {}   # momentum -> lists
         for g in self.param_groups:
             for p in g["params"]:
@@ -60,7 +61,10 @@ class SSNSGD(torch.optim.Optimizer):
                 b[3].append(g["lr"])
                 b[4].append(g["weight_decay"])
         for momentum, (ws, grads, bufs, lrs, wds) in batches.items():
-            K.sgd_step_multi(ws, grads, bufs, lrs, wds, momentum, grad_scale, False, skip_flag)
+            if grad_scale_dev is not None:
+                K.sgd_step_multi_dev(ws, grads, bufs, lrs, wds, momentum, grad_scale_dev, False, skip_flag)
+            else:
+                K.sgd_step_multi(ws, grads, bufs, lrs, wds, momentum, grad_scale, False, skip_flag)
         return None
 
 
@@ -85,3 +89,25 @@ def clip_grad_norm(parameters, max_norm):
                 p.grad = p.grad.contiguous()
             K.scale_(p.grad, None, clip_coef)
     return total_norm
+
+
+def clip_grad_norm_device(parameters, max_norm, pre_scale=1.0, out=None, workspace=None):
+    """The clipping of /root/reference/ssn_train.py:239-248 without a host read and in ceil(#tensors / 48) + 1 launches
+    (ssn_sumsq_multi), so that it can be captured into a hipGraph.  Returns the device tensor ``out`` [2]:
+
+        out[0] = total 2-norm of the gradients * pre_scale          (pre_scale = 1 / iter_size: the norm after ``p.grad /= iter_size``)
+        out[1] = pre_scale * max_norm / (out[0] + 1e-6) when that quotient is below 1, else pre_scale
+
+    UNLIKE the reference (and ``clip_grad_norm``), ``p.grad`` is left UNSCALED: out[1] is the factor the update has to apply, pass
+    ``out[1:]`` as ``SSNSGD.step(grad_scale_dev=)``.  ``max_norm`` None or <= 0: no clipping, out[1] = pre_scale.  A NaN norm leaves
+    the gradients unscaled, as the reference's ``clip_coef < 1`` test does.  Nothing is allocated when ``out`` (fp32 [2]) and
+    ``workspace`` (fp32, ``clip_workspace_floats(parameters)``) are passed.  Deterministic: two calls give the same bits."""
+    grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in parameters if p.grad is not None]
+    if not grads:
+        raise ValueError("clip_grad_norm_device: no parameter has a gradient")
+    return K.sumsq_multi(grads, pre_scale, 0.0 if max_norm is None else max_norm, out, workspace)
+
+
+def clip_workspace_floats(parameters):
+    """Workspace size (floats) of clip_grad_norm_device over these parameters, whether or not their gradients exist yet."""
+    return K.sumsq_multi_workspace_floats([p.numel() for p in parameters])

@@ -519,6 +519,35 @@ int ssn_sgd_step_multi(int count, float* const* w, const float* const* grad, flo
 /* clip_grad_norm support (ssn_train.py:245-249): out[0] (+)= sum(x^2); workspace >= 1024 floats. */
 int ssn_sumsq(const float* x, long n, float* out, int accumulate, float* workspace, hipStream_t stream);
 int ssn_scale(float* x, long n, const float* coef_dev, float coef, hipStream_t stream);
+/* ------------------------------------------------------------------ the training step's bookkeeping (csrc/train_step.hip)
+ * Meters, clipping and the optimizer of ssn_train.py:216-253 / binary_train.py:180-204 in a constant number of launches and without
+ * a host read (capturable into a hipGraph).  No atomics: every sum has a fixed order.
+ *
+ * ssn_step_meters: AverageMeter.update of all meters of one step, one launch of one workgroup.  logits fp32, `rows` rows of `cols`
+ * values row_stride (>= cols) elements apart; target int64 [rows]; losses device fp32 [n_losses], 0 <= n_losses <= 4.  state: device
+ * double [(n_losses + 3) * 4 + 1] = per meter {sum, count, last_num, last_den} (val = last_num / last_den, avg = sum / count), then
+ * the number of skipped calls.  Meters: the losses (n = loss_weight), top-1 accuracy over all rows (n = rows), over the even rows
+ * ("FG", n = rows / 2), over the odd rows ("BG").  An accuracy is float(correct) * float(100.0 / n_rows) in fp32 -- accuracy() of
+ * ssn_train.py:401-414 -- widened and accumulated in double.  Prediction of a row: its largest value, the lowest column among equals,
+ * NaN above every number, the first NaN taken; a target outside [0, cols) is a miss.  skip_flag (device int, may be null) non-zero:
+ * only the skipped counter changes (the convention of ssn_sgd_step_multi).  rows must be even and positive. */
+int ssn_step_meters(const float* logits, long row_stride, const long* target, int rows, int cols, const float* losses, int n_losses,
+                    double loss_weight, double* state, const int* skip_flag, hipStream_t stream);
+/* ssn_sumsq_multi: 2-norm over `count` fp32 tensors (HOST arrays of device pointers / lengths; zero lengths allowed; 4-byte
+ * alignment suffices) in ceil(count / 48) + 1 launches: one fp32 partial per 4096-element block in a fixed workspace slot, then one
+ * workgroup sums the partials in double in a fixed order.  out[0] = sqrt(sum x^2) * pre_scale; out[1] = the factor the update
+ * applies to the gradients: pre_scale * c when c = max_norm / (out[0] + 1e-6) < 1, else pre_scale (ssn_train.py:239-248 with
+ * pre_scale = 1 / iter_size).  max_norm <= 0: no clipping.  A NaN norm leaves out[1] = pre_scale, as the reference's test does.
+ * workspace: at least ssn_sumsq_multi_workspace_floats(count, n) floats. */
+long ssn_sumsq_multi_workspace_floats(int count, const long* n);
+int ssn_sumsq_multi(int count, const float* const* x, const long* n, float* workspace, long ws_floats, float pre_scale,
+                    float max_norm, float* out, hipStream_t stream);
+/* ssn_sgd_step_multi with grad_scale read from device memory (out + 1 of ssn_sumsq_multi): same update, same launches. */
+int ssn_sgd_step_multi_dev(int count, float* const* w, const float* const* grad, float* const* momentum_buf, const long* n,
+                           const float* lr, const float* weight_decay, float momentum, const float* grad_scale_dev,
+                           int first_step, const int* skip_flag, hipStream_t stream);
+/* Kernel launches the three entry points above have issued on the calling thread since the last reset (tests, profiling). */
+long ssn_train_step_launches(int reset);
 /* The stem (conv1_7x7_s2 of model_zoo.BNInception, behind ssn_models.py:266) on the split kernels through its space-to-depth
  * form: a k x k / stride-2 / pad (k-1)/2 convolution on C channels is a (k+1)/2-tap stride-1 convolution on the 4C channels
  * xs[(c*2+a)*2+b][h'][w'] = x[c][2h'+a][2w'+b], with 2 padding pixels in front and 1 behind (k = 7): forward =
