@@ -209,6 +209,7 @@ def test_conv_pl_dgrad(backend):
             dx.data.fill_(3.0)
             for _ in range(2):
                 P.conv_dgrad(P.pfull(gp), wt, P.pfull(dx), kh, kw, ph, pw, tile_cfg=tile, taps_reversed=rev)
+                assert abs(dx.amax.cpu().item() - dref.abs().max().item()) <= 1e-4 * dref.abs().max().item(), ("dx.amax", kh, kw, tile)
                 dx.pool.update()
             assert rel_err(P.to_f32(dx), dref) < 3e-6, ("dgrad", n, cin, h, cout, kh, kw, tile)
         # accumulate on top of itself, then the mask: dx <- (dx + dgrad) * (act > 0) * mscale
@@ -216,13 +217,16 @@ def test_conv_pl_dgrad(backend):
         msc = torch.randn(cin, generator=g)
         msc[::5] = float("nan")          # channels that are not ReLU outputs pass through
         actp = P.from_f32(backend.put(act))
+        m = torch.where(torch.isnan(msc).view(1, -1, 1, 1), torch.ones_like(act),
+                        (act > 0).float() * torch.nan_to_num(msc).view(1, -1, 1, 1)).double()
+        amax_ref = max(dref.abs().max().item(), (2 * dref * m).abs().max().item())
         for _ in range(2):
             P.conv_dgrad(P.pfull(gp), wt, P.pfull(dx), kh, kw, ph, pw, taps_reversed=rev)      # dx = d
             P.conv_dgrad(P.pfull(gp), wt, P.pfull(dx), kh, kw, ph, pw, accumulate=True, mask=P.pfull(actp),
                          mask_scale=backend.put(msc), taps_reversed=rev)                                          # dx = mask(2 d)
+            # (the slot keeps the larger of the two launches' maxima)
+            assert abs(dx.amax.cpu().item() - amax_ref) <= 1e-4 * amax_ref, ("dx.amax mask", n, cin, h, cout, kh, kw)
             dx.pool.update()
-        m = torch.where(torch.isnan(msc).view(1, -1, 1, 1), torch.ones_like(act),
-                        (act > 0).float() * torch.nan_to_num(msc).view(1, -1, 1, 1)).double()
         assert rel_err(P.to_f32(dx), 2 * dref * m) < 4e-6, ("dgrad mask", n, cin, h, cout, kh, kw)
 
 
@@ -444,6 +448,7 @@ def test_conv_pl_dgrad_stride2(backend):
         _two_pass(lambda: P.conv_dgrad_s2(P.pfull(gp), wt, P.pfull(dx), pad, mask=P.pfull(actp), mask_scale=backend.put(msc)), dx)
         ref = x.grad * (act > 0).double() * msc.double().view(1, -1, 1, 1)
         assert rel_err(P.to_f32(dx), ref) < 4e-6, (n, cin, h, cout, pad)
+        assert abs(dx.amax.cpu().item() - ref.abs().max().item()) <= 1e-4 * ref.abs().max().item(), ("dx.amax", n, cin, h, cout, pad)
 
 
 def test_planes_pools(backend):
