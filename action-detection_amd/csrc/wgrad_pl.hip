@@ -1318,10 +1318,11 @@ extern "C" long ssn_conv_wgrad_pl_workspace_bytes(int N, int Cin, int Cout, int 
     }
     if (tile_cfg >= 100 || (tile_cfg < 0 && kh == 3 && kw == 3)) {
         // (nine-tap kernel; a 3x3 layer that turns out not to qualify at launch needs at most the one-tap kernel's slabs below)
-        const int c9 = tile_cfg >= 100 ? tile_cfg - 100 : pick_tile9(Cout, Cin, Wo);
+        int c9 = tile_cfg >= 100 ? tile_cfg - 100 : pick_tile9(Cout, Cin, Wo);
+        if (c9 >= N9 || (xp_for(Wo) > 8 && c9 != 3)) c9 = 0;     // (wide rows run the 64 x 64 tiles only: plan the tile the launch takes)
         int splits9, cps9;
-        plan9(Cout, Cin, (long)N * (Ho + 1) * (Wo + 1), c9 < N9 ? c9 : 0, Wo, &splits9, &cps9);
-        const long need9 = (long)splits9 * k9KG[c9 < N9 ? c9 : 0] * Cout * ((long)Cin * 9 + 1) * (long)sizeof(float);
+        plan9(Cout, Cin, (long)N * (Ho + 1) * (Wo + 1), c9, Wo, &splits9, &cps9);
+        const long need9 = (long)splits9 * k9KG[c9] * Cout * ((long)Cin * 9 + 1) * (long)sizeof(float);
         if (tile_cfg >= 100) return need9;
         const int cfg1 = fix_cfg(-1, Cout, Cin);
         int s1, k1;
