@@ -1291,3 +1291,99 @@ def add_(dst, src):
 def scale_(x, coef_dev=None, coef=1.0):
     lib = _check(x, coef_dev)
     lib.call("ssn_scale", _p(x), x.numel(), _p(coef_dev), float(coef), _stream(lib, x))
+
+
+# ------------------------------------------------------------------------------------ TV-L1 optical flow (csrc/flow.hip)
+def tvl1_tile_shape():
+    """(th, tw, halo): the interior a workgroup of ssn_tvl1_iterate owns, and the most iterations one launch advances."""
+    lib = _lib.get_lib()
+    th, tw, halo = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    lib.call("ssn_tvl1_tile_shape", ctypes.byref(th), ctypes.byref(tw), ctypes.byref(halo))
+    return th.value, tw.value, halo.value
+
+
+def flow_gray(rgb):
+    """uint8 [..., H, W, 3] -> gray uint8 [..., H, W], (4899 R + 9617 G + 1868 B + 8192) >> 14."""
+    lib = _check(rgb)
+    if rgb.dtype != torch.uint8 or rgb.dim() < 3 or rgb.shape[-1] != 3:
+        raise ValueError("flow_gray: uint8 [..., H, W, 3] expected, got %s %s" % (rgb.dtype, tuple(rgb.shape)))
+    out = torch.empty(rgb.shape[:-1], device=rgb.device, dtype=torch.uint8)
+    n = out.numel()
+    lib.call("ssn_flow_gray", _p(rgb) if n else None, _p(out) if n else None, n, _stream(lib, rgb))
+    return out
+
+
+def flow_resize(src, size, mul_x=1.0, mul_y=1.0, out=None, src1=None, ctl=None):
+    """Bilinear resize (align_corners=False) of float32 [B, C, Hs, Ws] to [B, C, Hd, Wd]; plane c is multiplied by mul_x (c
+    even) or mul_y (c odd).  `src` / `out` may be channel-prefix views of wider contiguous [B, C', H, W] tensors.  With `ctl`
+    (int32 [B, 4]) batch element b is read from `src1` when its record says its state is in buffer 1."""
+    lib = _check(ctl)
+    for t in (src, src1, out):
+        if t is not None and (t.dim() != 4 or t.dtype != torch.float32 or t.stride(3) != 1 or t.stride(2) != t.shape[3]
+                              or t.stride(1) != t.shape[2] * t.shape[3]):
+            raise ValueError("flow_resize: float32 [B, C, H, W] with contiguous planes expected")
+        if t is not None and not lib.is_emulator and not t.is_cuda:
+            raise RuntimeError("SSN HIP ops need HIP (cuda) tensors; there is no CPU fallback")
+    b, c, hs, ws = src.shape
+    hd, wd = int(size[0]), int(size[1])
+    if out is None:
+        out = torch.empty((b, c, hd, wd), device=src.device, dtype=torch.float32)
+    if out.shape != (b, c, hd, wd):
+        raise ValueError("flow_resize: out must be [%d, %d, %d, %d]" % (b, c, hd, wd))
+    if (ctl is None) != (src1 is None) or (src1 is not None and (src1.shape != src.shape or src1.stride() != src.stride())):
+        raise ValueError("flow_resize: ctl and src1 come together, src1 laid out like src")
+    if ctl is not None and (ctl.dtype != torch.int32 or ctl.shape != (b, 4)):
+        raise ValueError("flow_resize: ctl must be int32 [B, 4]")
+    lib.call("ssn_flow_resize", _p(src), _p(src1), _p(ctl), _p(out), b, c, src.stride(0), out.stride(0), hs, ws, hd, wd,
+             float(mul_x), float(mul_y), _stream(lib, src))
+    return out
+
+
+def _tvl1_check(state, cst, ctl_in, ctl_out):
+    if state.dim() != 5 or state.shape[0] != 2 or state.shape[2] != 6 or state.dtype != torch.float32:
+        raise ValueError("tvl1: state must be float32 [2, B, 6, H, W]")
+    b, h, w = state.shape[1], state.shape[3], state.shape[4]
+    if cst.shape != (b, 4, h, w) or cst.dtype != torch.float32:
+        raise ValueError("tvl1: cst must be float32 [B, 4, H, W]")
+    for t in (ctl_in, ctl_out):
+        if t is not None and (t.dtype != torch.int32 or t.shape != (b, 4)):
+            raise ValueError("tvl1: a control record is int32 [B, 4]")
+    return b, h, w
+
+
+def tvl1_warp(i0, i1, state, cst, ctl_in, ctl_out):
+    """ssn_tvl1_warp: start a warp of every pair.  i0, i1 float32 [B, H, W]; state [2, B, 6, H, W]; cst [B, 4, H, W] (written);
+    ctl_in None: the state is in state[0]."""
+    lib = _check(i0, i1, state, cst, ctl_in, ctl_out)
+    b, h, w = _tvl1_check(state, cst, ctl_in, ctl_out)
+    if i0.shape != (b, h, w) or i1.shape != (b, h, w) or i0.dtype != torch.float32 or i1.dtype != torch.float32:
+        raise ValueError("tvl1_warp: images must be float32 [B, H, W]")
+    lib.call("ssn_tvl1_warp", _p(i0), _p(i1), _p(state[0]), _p(state[1]), _p(cst), _p(ctl_in), _p(ctl_out), b, h, w,
+             _stream(lib, state))
+
+
+def tvl1_iterate(state, cst, n_iter, l_t, theta, taut, err_thresh, ctl_in, ctl_out, part_in, part_out, iters):
+    """ssn_tvl1_iterate: n_iter iterations of every pair that is not done (see include/ssn_hip.h).  part_in / part_out float32
+    [B, tiles] or None; iters int32 [B]."""
+    lib = _check(state, cst, ctl_in, ctl_out, part_in, part_out, iters)
+    b, h, w = _tvl1_check(state, cst, ctl_in, ctl_out)
+    th, tw, _ = tvl1_tile_shape()
+    tiles = -(-h // th) * -(-w // tw)
+    for t in (part_in, part_out):
+        if t is not None and (t.dtype != torch.float32 or t.shape != (b, tiles)):
+            raise ValueError("tvl1_iterate: error partials must be float32 [%d, %d]" % (b, tiles))
+    if iters.dtype != torch.int32 or iters.shape != (b,):
+        raise ValueError("tvl1_iterate: iters must be int32 [B]")
+    lib.call("ssn_tvl1_iterate", _p(state[0]), _p(state[1]), _p(cst), b, h, w, int(n_iter), float(l_t), float(theta), float(taut),
+             float(err_thresh), _p(ctl_in), _p(ctl_out), _p(part_in), _p(part_out), _p(iters), _stream(lib, state))
+
+
+def flow_quantize(flow, bound):
+    """dense_flow's CAST: float32 flow -> uint8 of the same shape."""
+    lib = _check(flow)
+    if flow.dtype != torch.float32:
+        raise ValueError("flow_quantize: float32 expected")
+    out = torch.empty(flow.shape, device=flow.device, dtype=torch.uint8)
+    n = flow.numel()
+    lib.call("ssn_flow_quantize", _p(flow) if n else None, _p(out) if n else None, n, float(bound), _stream(lib, flow))
+    return out

@@ -700,6 +700,34 @@ int ssn_pl_bn_train_bwd(const void* dy_hi, const void* dy_lo, long dy_img_groups
                         void* dz_lo, long dz_img_groups, const float* dz_scale, float* dz_amax, float* dz_f32,
                         long dz_f32_img_stride, int N, int C, int HW, void* workspace, long ws_bytes, hipStream_t stream);
 
+/* TV-L1 optical flow for the Flow modality (csrc/flow.hip): the stage the reference's README hands to dense_flow (OpenCV's CUDA
+ * OpticalFlowDual_TVL1).  The algorithm, its parameters and the standing of its parity are in DESIGN.md section 3.9.  Images are
+ * fp32 [B][H][W] gray in [0, 255]; a level's state is two buffers [B][6][H][W] (u1, u2, p11, p12, p21, p22) and the per-warp
+ * constants cst [B][4][H][W] (gx, gy, grad, rho_c).  ctl is a per-pair record int32 [B][4] = {done, launches, iterations, 0}: the
+ * pair's current state is in buffer (launches & 1); every call that takes ctl_in / ctl_out reads one slot and writes ANOTHER
+ * (the caller alternates two), so that no workgroup reads a word that another workgroup of the same launch writes.  Nothing here
+ * reads back to the host: the caller enqueues the worst-case number of launches and the workgroups of a finished pair exit.
+ *  gray      (4899 R + 9617 G + 1868 B + 8192) >> 14 on uint8 [pixels][3].
+ *  resize    bilinear, source coordinate (d + 0.5) * src / dst - 0.5, indices clamped; plane c of a batch element is multiplied by
+ *            mul_x (c even) or mul_y (c odd).  With ctl, element b is read from src1 when its state is in buffer 1.
+ *  warp      starts a warp: brings the pair's state to state0, samples I1 and its centred gradient at (x + u1, y + u2) clamped to
+ *            the image, writes cst and a fresh record.  ctl_in NULL: the state is in state0 (first warp of a level).
+ *  iterate   n_iter (1 .. halo) iterations of every pair that is not done.  part_in [B][tiles] or NULL: the error partials of
+ *            the chunk the previous launch ended, summed in tile order and tested against err_thresh by every workgroup;
+ *            part_out [B][tiles] or NULL: this launch ends a chunk and writes its last iteration's partials.  iters [B] follows
+ *            the pair's iteration count.  tiles = ceil(H / th) * ceil(W / tw) of the tile shape below.
+ *  quantize  dense_flow's CAST, in fp32: v > bound -> 255, v < -bound -> 0, else rintf(255 (v + bound) / (2 bound)). */
+int ssn_tvl1_tile_shape(int* th, int* tw, int* halo);
+int ssn_flow_gray(const unsigned char* rgb, unsigned char* gray, long pixels, hipStream_t stream);
+int ssn_flow_resize(const float* src0, const float* src1, const int* ctl, float* dst, int B, int C, long src_bstride, long dst_bstride,
+                    int Hs, int Ws, int Hd, int Wd, float mul_x, float mul_y, hipStream_t stream);
+int ssn_tvl1_warp(const float* I0, const float* I1, float* state0, const float* state1, float* cst, const int* ctl_in, int* ctl_out,
+                  int B, int H, int W, hipStream_t stream);
+int ssn_tvl1_iterate(float* state0, float* state1, const float* cst, int B, int H, int W, int n_iter, float l_t, float theta,
+                     float taut, float err_thresh, const int* ctl_in, int* ctl_out, const float* part_in, float* part_out, int* iters,
+                     hipStream_t stream);
+int ssn_flow_quantize(const float* flow, unsigned char* out, long n, float bound, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
