@@ -1387,3 +1387,69 @@ def flow_quantize(flow, bound):
     n = flow.numel()
     lib.call("ssn_flow_quantize", _p(flow) if n else None, _p(out) if n else None, n, float(bound), _stream(lib, flow))
     return out
+
+
+# ------------------------------------------------------------------------------------ baseline JPEG decoding (csrc/jpeg.hip)
+def jpeg_layout():
+    """(desc_ints, unit_ints, table_words, lds_sets): row sizes of the tables jpeg_decode.py builds, and the table sets a workgroup
+    of ssn_jpeg_entropy holds."""
+    lib = _lib.get_lib()
+    v = [ctypes.c_int() for _ in range(4)]
+    lib.call("ssn_jpeg_layout", *[ctypes.byref(x) for x in v])
+    return tuple(x.value for x in v)
+
+
+def _jpeg_desc(desc):
+    if desc.dtype != torch.int32 or desc.dim() != 2 or desc.shape[1] != jpeg_layout()[0] or desc.shape[0] < 1:
+        raise ValueError("jpeg: desc must be int32 [images, %d]" % jpeg_layout()[0])
+    return desc.shape[0]
+
+
+def jpeg_entropy(bits, desc, units, tables, coef, status):
+    """ssn_jpeg_entropy: bits uint8 [bytes]; desc int32 [images, desc_ints]; units int32 [64 k, unit_ints]; tables int32
+    [sets, 4, table_words]; coef int16 [blocks, 64] and status int32 [images] are zeroed, then written."""
+    lib = _check(bits, desc, units, tables, coef, status)
+    n = _jpeg_desc(desc)
+    _, unit_ints, table_words, _ = jpeg_layout()
+    if bits.dtype != torch.uint8 or bits.dim() != 1:
+        raise ValueError("jpeg_entropy: bits must be uint8 [bytes]")
+    if units.dtype != torch.int32 or units.dim() != 2 or units.shape[1] != unit_ints or units.shape[0] < 64 or units.shape[0] % 64:
+        raise ValueError("jpeg_entropy: units must be int32 [64 k, %d]" % unit_ints)
+    if tables.dtype != torch.int32 or tables.dim() != 3 or tables.shape[1:] != (4, table_words) or tables.shape[0] < 1:
+        raise ValueError("jpeg_entropy: tables must be int32 [sets, 4, %d]" % table_words)
+    if coef.dtype != torch.int16 or coef.dim() != 2 or coef.shape[1] != 64 or coef.shape[0] < 1:
+        raise ValueError("jpeg_entropy: coef must be int16 [blocks, 64]")
+    if status.dtype != torch.int32 or status.shape != (n,):
+        raise ValueError("jpeg_entropy: status must be int32 [images]")
+    lib.call("ssn_jpeg_entropy", _p(bits) if bits.numel() else None, bits.numel(), _p(desc), n, _p(units), units.shape[0], _p(tables),
+             tables.shape[0], _p(coef), coef.shape[0], _p(status), _stream(lib, coef))
+
+
+def jpeg_idct(coef, desc, max_blocks, quant, planes):
+    """ssn_jpeg_idct: coef int16 [blocks, 64]; quant int16 [n, 64] (the 8-bit tables, natural order); planes uint8 [bytes] (written)."""
+    lib = _check(coef, desc, quant, planes)
+    n = _jpeg_desc(desc)
+    if coef.dtype != torch.int16 or coef.dim() != 2 or coef.shape[1] != 64 or coef.shape[0] < 1:
+        raise ValueError("jpeg_idct: coef must be int16 [blocks, 64]")
+    if quant.dtype != torch.int16 or quant.dim() != 2 or quant.shape[1] != 64 or quant.shape[0] < 1:
+        raise ValueError("jpeg_idct: quant must be int16 [n, 64]")
+    if planes.dtype != torch.uint8 or planes.dim() != 1 or planes.numel() < 64 or planes.data_ptr() % 8:
+        raise ValueError("jpeg_idct: planes must be uint8 [bytes], 8-byte aligned, at least one block")
+    if int(max_blocks) < 1:
+        raise ValueError("jpeg_idct: max_blocks must be positive")
+    lib.call("ssn_jpeg_idct", _p(coef), coef.shape[0], _p(desc), n, int(max_blocks), _p(quant), quant.shape[0], _p(planes),
+             planes.numel(), _stream(lib, planes))
+
+
+def jpeg_pixels(planes, desc, max_pixels, out_c, out):
+    """ssn_jpeg_pixels: planes uint8 [bytes]; out uint8 [bytes] (written: [H, W, out_c] per image at its offset)."""
+    lib = _check(planes, desc, out)
+    n = _jpeg_desc(desc)
+    if planes.dtype != torch.uint8 or planes.dim() != 1 or planes.numel() < 64:
+        raise ValueError("jpeg_pixels: planes must be uint8 [bytes]")
+    if out.dtype != torch.uint8 or out.dim() != 1 or out.numel() < 1:
+        raise ValueError("jpeg_pixels: out must be uint8 [bytes]")
+    if out_c not in (1, 3) or int(max_pixels) < 1:
+        raise ValueError("jpeg_pixels: out_c is 1 or 3, max_pixels positive")
+    lib.call("ssn_jpeg_pixels", _p(planes), planes.numel(), _p(desc), n, int(max_pixels), int(out_c), _p(out), out.numel(),
+             _stream(lib, out))

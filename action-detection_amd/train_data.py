@@ -38,6 +38,26 @@ class FrameDirReader(object):
         return np.stack(out)
 
 
+class CompressedFrameDirReader(FrameDirReader):
+    """The same files as ``FrameDirReader``, undecoded: -> list of ``bytes``, one per image (Flow: x then y), for
+    ``jpeg_decode.CompressedBatchPrefetcher``, which decodes them on the device."""
+
+    def _open(self, path, mode):
+        with open(path, "rb") as f:
+            return f.read()
+
+    def __call__(self, video_id, indices):
+        d = video_id if os.path.isabs(video_id) else os.path.join(self.root, video_id)
+        out = []
+        for i in indices:
+            if self.modality in ("RGB", "RGBDiff"):
+                out.append(self._open(os.path.join(d, "img_{:05d}.jpg".format(int(i))), "RGB"))
+            else:
+                out.append(self._open(os.path.join(d, self.flow_prefix + "x_{:05d}.jpg".format(int(i))), "L"))
+                out.append(self._open(os.path.join(d, self.flow_prefix + "y_{:05d}.jpg".format(int(i))), "L"))
+        return out
+
+
 class SyntheticReader(object):
     """Seeded noise frames of the decoded size, a stand-in for a frame directory (``--synthetic``)."""
 
@@ -80,6 +100,39 @@ def binary_batches(sampler, reader, videos_per_batch=4, order=None, drop_last=Tr
             group = []
     if group and not drop_last:
         yield tuple(np.stack(x) for x in zip(*group))
+
+
+def _file_batches(rows, videos_per_batch, drop_last):
+    group = []
+    for row in rows:
+        group.append(row)
+        if len(group) == videos_per_batch:
+            yield (tuple(g[0] for g in group),) + tuple(np.stack(x) for x in list(zip(*group))[1:])
+            group = []
+    if group and not drop_last:
+        yield (tuple(g[0] for g in group),) + tuple(np.stack(x) for x in list(zip(*group))[1:])
+
+
+def compressed_ssn_batches(sampler, reader, videos_per_batch, order=None, drop_last=True):
+    """``ssn_batches`` with a ``CompressedFrameDirReader``: the first field is, per video, the list of its files' bytes."""
+    def rows():
+        for index in (range(len(sampler)) if order is None else order):
+            props, arr = sampler.sample_video(index)
+            files = [b for p in props for b in reader(p.video_id, p.frame_indices)]
+            yield files, arr["scaling"], arr["labels"].astype(np.int64), arr["reg_targets"], arr["prop_type"].astype(np.int64)
+    return _file_batches(rows(), videos_per_batch, drop_last)
+
+
+def compressed_binary_batches(sampler, reader, videos_per_batch=4, order=None, drop_last=True):
+    """``binary_batches`` with a ``CompressedFrameDirReader``."""
+    def rows():
+        for index in (range(len(sampler)) if order is None else order):
+            props, arr = sampler.sample_video(index)
+            files = [b for p in props for b in reader(p.video_id, p.frame_indices)]
+            n = len(props)
+            yield (files, np.zeros((n, 2), np.float32), np.zeros(n, np.int64), np.zeros((n, 2), np.float32),
+                   arr["prop_type"].astype(np.int64))
+    return _file_batches(rows(), videos_per_batch, drop_last)
 
 
 def synthetic_ssn_source(n_batches, videos_per_batch, num_class, modality="RGB", new_length=1, hw=(256, 340), seed=0,

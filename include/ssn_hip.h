@@ -728,6 +728,28 @@ int ssn_tvl1_iterate(float* state0, float* state1, const float* cst, int B, int 
                      hipStream_t stream);
 int ssn_flow_quantize(const float* flow, unsigned char* out, long n, float bound, hipStream_t stream);
 
+/* Baseline JPEG decoding of a batch of files (csrc/jpeg.hip): what the reference's loader workers do with PIL in _load_image,
+ * Image.open(path).convert('RGB') / .convert('L') (ssn_dataset.py:208-215), bit for bit (libjpeg's islow inverse DCT, fancy upsampling
+ * and 16-bit colour conversion).  The host walks the markers (jpeg_decode.py) and describes the batch in
+ * device tables: desc int32 [images][desc_ints], units int32 [units][unit_ints] (one row per restart interval or per scan, padded
+ * with image = -1 to rows of 64), tables uint32 [sets][4][table_words] (the distinct Huffman table sets: per table 512 16-bit
+ * first-level entries (length << 8 | symbol, 0: longer than 9 bits), maxcode[17], valoff[17], 256 symbols), quant uint16 [n][64] in
+ * natural order.  A workgroup of the entropy stage stages at most lds_sets consecutive sets.
+ *  layout    the four sizes above.
+ *  entropy   replaces the Huffman decoding inside Image.open: zero-fills coef int16 [total_blocks][64] (natural order) and status
+ *            int32 [images], then one lane per unit.  A unit that runs out of data (1), meets an undefined code (2), overruns a
+ *            block (4) or has an unusable table row (8) ORs that bit into its image's status word and stops.
+ *  idct      replaces libjpeg's dequantisation + jpeg_idct_islow: coef -> uint8 component planes padded to whole MCUs.
+ *  pixels    replaces libjpeg's upsampling, YCbCr -> RGB conversion and PIL's .convert(mode): planes -> uint8 [H][W][out_c] per
+ *            image at its output offset, out_c 3 (RGB) or 1 (L). */
+int ssn_jpeg_layout(int* desc_ints, int* unit_ints, int* table_words, int* lds_sets);
+int ssn_jpeg_entropy(const unsigned char* bits, long bits_bytes, const int* desc, int n_images, const int* units, int n_units,
+                     const unsigned int* tables, int n_sets, short* coef, long total_blocks, int* status, hipStream_t stream);
+int ssn_jpeg_idct(const short* coef, long total_blocks, const int* desc, int n_images, int max_blocks, const unsigned short* quant,
+                  int n_quant, unsigned char* planes, long plane_bytes, hipStream_t stream);
+int ssn_jpeg_pixels(const unsigned char* planes, long plane_bytes, const int* desc, int n_images, long max_pixels, int out_c,
+                    unsigned char* out, long out_bytes, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

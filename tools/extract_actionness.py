@@ -47,20 +47,59 @@ def frame_batches(load, video, sampler, transform, gen_batch=4):
         yield transform(frames)
 
 
-def extract(net, sampler, load, test_crops=10, input_size=None, tick_batch=32, grouping="reference", max_num=-1, verbose=True):
-    """-> ActionnessScores of the first max_num (all) videos of the sampler's list; ``net`` as ActionnessTester takes it."""
+def file_reader(frame_root, modality, flow_pref=""):
+    """The same files as ``pil_loader``, undecoded: read(video id, frame number) -> [bytes]."""
+    def read(vid, idx):
+        folder = os.path.join(frame_root, vid)
+        names = ["img_{:05d}.jpg".format(idx)] if modality == "RGB" else ["{}{}_{:05d}.jpg".format(flow_pref, p, idx) for p in "xy"]
+        out = []
+        for name in names:
+            with open(os.path.join(folder, name), "rb") as f:
+                out.append(f.read())
+        return out
+    return read
+
+
+def device_transform(net, modality, device, input_size=None):
+    """--gpu-decode: [bytes] -> what ``transform(frames)`` of ``extract`` yields for 10 crops, with the files decoded on the device
+    (jpeg_decode.JpegDecoder) and GroupOverSample -> Stack -> ToTorchFormatTensor -> GroupNormalize as one launch
+    (input_pipeline.GpuFrameTransform).  GroupOverSample's GroupScale(scale_size) is the identity on frames whose short side is
+    scale_size already -- the 340 x 256 frames the extraction scripts write; other sizes are refused."""
+    from action_detection_amd.input_pipeline import GpuFrameTransform
+    from action_detection_amd.jpeg_decode import JpegDecoder
+    decoder = JpegDecoder(device)
+    tf = GpuFrameTransform(net.input_size if input_size is None else input_size, net.input_mean, net.input_std, roll=True,
+                           is_flow=modality == "Flow", device=device)
+
+    def transform(blobs):
+        frames = decoder.decode(blobs, "RGB" if modality == "RGB" else "L", stack=True)
+        if min(frames.shape[1], frames.shape[2]) != net.scale_size:
+            raise ValueError("--gpu-decode needs frames whose short side is %d, got %d x %d" % (net.scale_size, frames.shape[2], frames.shape[1]))
+        return tf.oversample(frames)
+    return transform
+
+
+def extract(net, sampler, load, test_crops=10, input_size=None, tick_batch=32, grouping="reference", max_num=-1, verbose=True,
+            transform=None):
+    """-> ActionnessScores of the first max_num (all) videos of the sampler's list; ``net`` as ActionnessTester takes it.
+    ``transform``: replaces the host chain (``device_transform`` with a ``file_reader`` as ``load``)."""
     import time
     from action_detection_amd import transforms as T
     from action_detection_amd.actionness_test import ActionnessTester
     input_size = net.input_size if input_size is None else input_size
-    if test_crops == 1:
+    if transform is not None:
+        if test_crops != 10:
+            raise ValueError("a device transform yields the 10 crops of GroupOverSample, got test_crops = {}".format(test_crops))
+        cropping = None
+    elif test_crops == 1:
         cropping = [T.GroupScale(net.scale_size), T.GroupScale(input_size)]
     elif test_crops == 10:
         cropping = [T.GroupOverSample(input_size, net.scale_size)]
     else:
         raise ValueError("only 1 and 10 crops are supported while we got {}".format(test_crops))
-    transform = T.Compose(cropping + [T.Stack(roll=True), T.ToTorchFormatTensor(div=False),
-                                      T.GroupNormalize(net.input_mean, net.input_std)])
+    if transform is None:
+        transform = T.Compose(cropping + [T.Stack(roll=True), T.ToTorchFormatTensor(div=False),
+                                          T.GroupNormalize(net.input_mean, net.input_std)])
     tester = ActionnessTester(net, tick_batch=tick_batch, grouping=grouping)
     videos = sampler.video_list if max_num <= 0 else sampler.video_list[:max_num]
     start = time.time()
@@ -90,6 +129,7 @@ def main(argv=None):
     ap.add_argument("--tick_batch", type=int, default=32)
     ap.add_argument("--grouping", type=str, default="reference", choices=["reference", "tick"])
     ap.add_argument("--device", type=str, default="cuda:0")
+    ap.add_argument("--gpu-decode", action="store_true", help="decode the frames on the device (10 crops, frames at scale_size)")
     args = ap.parse_args(argv)
 
     import torch
@@ -105,8 +145,13 @@ def main(argv=None):
     net.prepare_test_fc()
     net.to(args.device).eval()
     sampler = ActionnessSampler(args.proposal_list, new_length=data_length, test_interval=args.frame_interval)
-    scores = extract(net, sampler, pil_loader(args.frame_root, args.modality, args.flow_pref), args.test_crops, args.input_size,
-                     args.tick_batch, args.grouping, args.max_num)
+    if args.gpu_decode:
+        scores = extract(net, sampler, file_reader(args.frame_root, args.modality, args.flow_pref), args.test_crops, args.input_size,
+                         args.tick_batch, args.grouping, args.max_num,
+                         transform=device_transform(net, args.modality, args.device, args.input_size))
+    else:
+        scores = extract(net, sampler, pil_loader(args.frame_root, args.modality, args.flow_pref), args.test_crops, args.input_size,
+                         args.tick_batch, args.grouping, args.max_num)
     scores.save(args.save_scores)
     print("wrote {} videos to {}".format(len(scores), args.save_scores))
     return scores

@@ -46,6 +46,15 @@ def load_frames(folder, n):
     return np.stack(frames)
 
 
+def load_frames_on_device(folder, n, decoder):
+    """The same frames, decoded on the device (--gpu-decode): only the files' bytes are uploaded."""
+    blobs = []
+    for i in range(1, n + 1):
+        with open(os.path.join(folder, "img_{:05d}.jpg".format(i)), "rb") as f:
+            blobs.append(f.read())
+    return decoder.decode(blobs, "RGB", stack=True)
+
+
 def write_flow(folder, prefix, flow_u8, quality):
     from PIL import Image
     os.makedirs(folder, exist_ok=True)
@@ -63,6 +72,7 @@ def main(argv=None):
     ap.add_argument("--pair-batch", type=int, default=16)
     ap.add_argument("--iterations", type=int, default=300)
     ap.add_argument("--jpeg-quality", type=int, default=95)
+    ap.add_argument("--gpu-decode", action="store_true", help="decode the input frames on the device (jpeg_decode.JpegDecoder)")
     ap.add_argument("--quiet", action="store_true")
     args = ap.parse_args(argv)
 
@@ -71,12 +81,19 @@ def main(argv=None):
     from action_detection_amd.optical_flow import TVL1, FlowExtractor
     dev = torch.device("cpu") if _lib.emulator_active() else torch.device("cuda")
     extractor = FlowExtractor(TVL1(iterations=args.iterations), bound=args.bound, pair_batch=args.pair_batch)
+    decoder = None
+    if args.gpu_decode:
+        from action_detection_amd.jpeg_decode import JpegDecoder
+        decoder = JpegDecoder(dev)
     videos = video_dirs(args.src_root)
     if not videos:
         print("no directory with img_00001.jpg, img_00002.jpg, ... under %s" % args.src_root, file=sys.stderr)
         return 1
     for rel, n in videos:
-        frames = torch.from_numpy(load_frames(os.path.join(args.src_root, rel), n)).to(dev)
+        if decoder is not None:
+            frames = load_frames_on_device(os.path.join(args.src_root, rel), n, decoder)
+        else:
+            frames = torch.from_numpy(load_frames(os.path.join(args.src_root, rel), n)).to(dev)
         flow = extractor.extract(frames).cpu().numpy()
         write_flow(os.path.join(args.out_root, rel), args.flow_prefix, flow, args.jpeg_quality)
         if not args.quiet:

@@ -44,6 +44,8 @@ def parse(argv=None):
     p.add_argument("--frame-root", default="")
     p.add_argument("--synthetic", type=int, default=0, metavar="N", help="N seeded batches instead of a data set")
     p.add_argument("--device", default="cuda:0")
+    p.add_argument("--gpu-decode", action="store_true",
+                   help="upload the frames' JPEG files and decode them on the device (jpeg_decode.py) instead of PIL on the host")
     return p.parse_args(argv)
 
 
@@ -83,6 +85,7 @@ def main(argv=None):
     train_tf, val_tf = D.make_transforms(model, args.device)
     snippets = args.num_body_segments * new_length * (1 if args.modality == "RGB" else 2)
 
+    Prefetcher, batches = TrainingBatchPrefetcher, D.binary_batches
     if args.synthetic:
         n_train = n_val = args.synthetic
 
@@ -96,23 +99,28 @@ def main(argv=None):
     else:
         if not (args.train_list and args.val_list and args.frame_root):
             raise SystemExit("--train-list, --val-list and --frame-root are needed without --synthetic")
-        reader = D.FrameDirReader(args.frame_root, args.modality, args.flow_prefix)
+        if args.gpu_decode:
+            from action_detection_amd.jpeg_decode import CompressedBatchPrefetcher
+            Prefetcher, batches = CompressedBatchPrefetcher, D.compressed_binary_batches
+            reader = D.CompressedFrameDirReader(args.frame_root, args.modality, args.flow_prefix)
+        else:
+            reader = D.FrameDirReader(args.frame_root, args.modality, args.flow_prefix)
         common = dict(body_seg=args.num_body_segments, new_length=new_length)
         train_sampler = ActionnessSampler(args.train_list, epoch_multiplier=args.training_epoch_multiplier, **common)
         val_sampler = ActionnessSampler(args.val_list, random_shift=False, fg_ratio=6, bg_ratio=6, **common)
         n_train, n_val = len(train_sampler) // args.batch_size, -(-len(val_sampler) // args.batch_size)
 
         def train_source(epoch):
-            return D.binary_batches(train_sampler, reader, args.batch_size, np.random.permutation(len(train_sampler)))
+            return batches(train_sampler, reader, args.batch_size, np.random.permutation(len(train_sampler)))
 
         def val_source(epoch):
-            return D.binary_batches(val_sampler, reader, args.batch_size, drop_last=False)
+            return batches(val_sampler, reader, args.batch_size, drop_last=False)
 
     def train_batches(epoch):
-        return D.Counted(D.binary_view(D.closing(TrainingBatchPrefetcher(train_source(epoch), train_tf, group_size=snippets))), n_train)
+        return D.Counted(D.binary_view(D.closing(Prefetcher(train_source(epoch), train_tf, group_size=snippets))), n_train)
 
     def val_batches(epoch):
-        return D.Counted(D.binary_view(D.closing(TrainingBatchPrefetcher(val_source(epoch), val_tf, group_size=snippets))), n_val)
+        return D.Counted(D.binary_view(D.closing(Prefetcher(val_source(epoch), val_tf, group_size=snippets))), n_val)
 
     trainer = BinaryTrainer(model, optimizer, lr_steps=args.lr_steps, iter_size=args.iter_size, clip_gradient=args.clip_gradient,
                             print_freq=args.print_freq)

@@ -57,6 +57,8 @@ def parse(argv=None):
     p.add_argument("--frame-root", default="")
     p.add_argument("--synthetic", type=int, default=0, metavar="N", help="N seeded batches instead of a data set")
     p.add_argument("--device", default="cuda:0")
+    p.add_argument("--gpu-decode", action="store_true",
+                   help="upload the frames' JPEG files and decode them on the device (jpeg_decode.py) instead of PIL on the host")
     return p.parse_args(argv)
 
 
@@ -98,6 +100,7 @@ def main(argv=None):
     train_tf, val_tf = D.make_transforms(model, args.device)
     snippets = (2 * args.num_aug_segments + args.num_body_segments) * new_length * (1 if args.modality == "RGB" else 2)
 
+    Prefetcher, batches = TrainingBatchPrefetcher, D.ssn_batches
     if args.synthetic:
         reg_stats = np.array([[0.0, 0.0], [1.0, 1.0]])
         split, group_size = 1, 7
@@ -111,7 +114,12 @@ def main(argv=None):
     else:
         if not (args.train_list and args.val_list and args.frame_root):
             raise SystemExit("--train-list, --val-list and --frame-root are needed without --synthetic")
-        reader = D.FrameDirReader(args.frame_root, args.modality, args.flow_prefix)
+        if args.gpu_decode:
+            from action_detection_amd.jpeg_decode import CompressedBatchPrefetcher
+            Prefetcher, batches = CompressedBatchPrefetcher, D.compressed_ssn_batches
+            reader = D.CompressedFrameDirReader(args.frame_root, args.modality, args.flow_prefix)
+        else:
+            reader = D.FrameDirReader(args.frame_root, args.modality, args.flow_prefix)
         common = dict(body_seg=args.num_body_segments, aug_seg=args.num_aug_segments, new_length=new_length)
         train_sampler = ProposalSampler(args.train_list, **common)
         val_sampler = ProposalSampler(args.val_list, random_shift=False, reg_stats=train_sampler.stats, **common)
@@ -122,16 +130,16 @@ def main(argv=None):
 
         def train_source(epoch):
             order = np.random.permutation(len(train_sampler) * args.training_epoch_multiplier)
-            return D.ssn_batches(train_sampler, reader, args.batch_size, order)
+            return batches(train_sampler, reader, args.batch_size, order)
 
         def val_source(epoch):
-            return D.ssn_batches(val_sampler, reader, args.batch_size, drop_last=False)
+            return batches(val_sampler, reader, args.batch_size, drop_last=False)
 
     def train_batches(epoch):
-        return D.Counted(D.closing(TrainingBatchPrefetcher(train_source(epoch), train_tf, group_size=snippets)), n_train)
+        return D.Counted(D.closing(Prefetcher(train_source(epoch), train_tf, group_size=snippets)), n_train)
 
     def val_batches(epoch):
-        return D.Counted(D.closing(TrainingBatchPrefetcher(val_source(epoch), val_tf, group_size=snippets)), n_val)
+        return D.Counted(D.closing(Prefetcher(val_source(epoch), val_tf, group_size=snippets)), n_val)
 
     trainer = SSNTrainer(model, optimizer, SSNObjective(args.comp_loss_weight, args.reg_loss_weight), sample_split=split,
                          sample_group_size=group_size, lr_steps=args.lr_steps, iter_size=args.iter_size,
