@@ -19,7 +19,7 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(_HERE, "libssn_hip.so")
-SOURCES = ["conv_igemm.hip", "conv_x6.hip", "conv_x6_rect.hip", "conv_wgrad.hip", "conv_wgrad_x6.hip", "elementwise.hip", "bn_train.hip", "frames.hip", "detect.hip", "pool.hip", "stpp.hip", "heads_losses.hip", "conv_pl.hip", "planes_ops.hip", "planes_bn.hip", "wgrad_pl.hip", "tag.hip", "eval.hip", "actionness.hip", "train_step.hip", "flow.hip", "jpeg.hip"]
+SOURCES = ["conv_igemm.hip", "conv_x6.hip", "conv_x6_rect.hip", "conv_wgrad.hip", "conv_wgrad_x6.hip", "elementwise.hip", "bn_train.hip", "frames.hip", "detect.hip", "pool.hip", "stpp.hip", "heads_losses.hip", "conv_pl.hip", "planes_ops.hip", "planes_bn.hip", "wgrad_pl.hip", "tag.hip", "eval.hip", "actionness.hip", "train_step.hip", "flow.hip", "jpeg.hip", "jpeg_encode.hip"]
 
 STPP_MAX_PARTS = 24
 
@@ -92,6 +92,12 @@ _SIGS = {
     "ssn_jpeg_entropy": "plpipipiplpp",
     "ssn_jpeg_idct": "plpiipiplp",
     "ssn_jpeg_pixels": "plpiliplp",
+    "ssn_jpeg_enc_layout": "pp",
+    "ssn_jpeg_enc_blocks": "plpiipplp",
+    "ssn_jpeg_enc_count": "plpiipppp",
+    "ssn_jpeg_enc_scan": "piplplppp",
+    "ssn_jpeg_enc_pack": "plpiippplpplpp",
+    "ssn_jpeg_enc_assemble": "plpiplpplpplpppp",
     "ssn_frames_crop_normalize": "ppiiiiiiipppiipipip",
     "ssn_frames_crop_resize_normalize": "ppiiiiiippiipipipup",
     "ssn_reg_denorm": "plffffp",

@@ -1453,3 +1453,97 @@ def jpeg_pixels(planes, desc, max_pixels, out_c, out):
         raise ValueError("jpeg_pixels: out_c is 1 or 3, max_pixels positive")
     lib.call("ssn_jpeg_pixels", _p(planes), planes.numel(), _p(desc), n, int(max_pixels), int(out_c), _p(out), out.numel(),
              _stream(lib, out))
+
+
+# ------------------------------------------------------------------------------------ baseline JPEG encoding (csrc/jpeg_encode.hip)
+def jpeg_enc_layout():
+    """(desc_ints, block_bits): ints of a desc row jpeg_encode.py builds, and the most bits the codes of one block take."""
+    lib = _lib.get_lib()
+    v = [ctypes.c_int() for _ in range(2)]
+    lib.call("ssn_jpeg_enc_layout", *[ctypes.byref(x) for x in v])
+    return tuple(x.value for x in v)
+
+
+def _jpeg_enc_common(who, desc, coef=None, tables=None, blkbits=None, ivals=None, rawlen=None, status=None, raw=None):
+    """Shape and dtype checks the encoder wrappers share -> number of images."""
+    if desc.dtype != torch.int32 or desc.dim() != 2 or desc.shape[1] != jpeg_enc_layout()[0] or not 1 <= desc.shape[0] <= 65535:
+        raise ValueError("%s: desc must be int32 [images, %d], 1 .. 65535 images" % (who, jpeg_enc_layout()[0]))
+    n = desc.shape[0]
+    if coef is not None and (coef.dtype != torch.int16 or coef.dim() != 2 or coef.shape[1] != 64 or not 1 <= coef.shape[0] < (1 << 25)
+                             or coef.data_ptr() % 4):
+        raise ValueError("%s: coef must be int16 [blocks, 64], fewer than 2^25 blocks" % who)
+    if tables is not None and (tables.dtype != torch.int32 or tuple(tables.shape) != (4, 256)):
+        raise ValueError("%s: tables must be int32 [4, 256]" % who)
+    if blkbits is not None and (blkbits.dtype != torch.int32 or blkbits.dim() != 1 or (coef is not None and blkbits.shape[0] != coef.shape[0])
+                                or not 1 <= blkbits.shape[0] < (1 << 25)):
+        raise ValueError("%s: blkbits must be int32 [blocks]" % who)
+    if ivals is not None and (ivals.dtype != torch.int32 or ivals.dim() != 1 or ivals.shape[0] < 1):
+        raise ValueError("%s: ivals must be int32 [intervals]" % who)
+    for name, t in (("rawlen", rawlen), ("status", status)):
+        if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != (n,)):
+            raise ValueError("%s: %s must be int32 [images]" % (who, name))
+    if raw is not None and (raw.dtype != torch.uint8 or raw.dim() != 1 or raw.numel() < 4 or raw.numel() % 4 or raw.numel() >= (1 << 31)
+                            or raw.data_ptr() % 4):
+        raise ValueError("%s: raw must be uint8 [bytes], a multiple of 4 below 2^31, 4-byte aligned" % who)
+    return n
+
+
+def jpeg_enc_blocks(pix, desc, max_blocks, quant, coef):
+    """ssn_jpeg_enc_blocks: pix uint8 [bytes]; quant int16 [2, 64] (natural order, 1 .. 255); coef int16 [blocks, 64] (written)."""
+    lib = _check(pix, desc, quant, coef)
+    n = _jpeg_enc_common("jpeg_enc_blocks", desc, coef=coef)
+    if pix.dtype != torch.uint8 or pix.dim() != 1 or not 1 <= pix.numel() < (1 << 31):
+        raise ValueError("jpeg_enc_blocks: pix must be uint8 [bytes], fewer than 2^31")
+    if quant.dtype != torch.int16 or tuple(quant.shape) != (2, 64):
+        raise ValueError("jpeg_enc_blocks: quant must be int16 [2, 64]")
+    if int(max_blocks) < 1:
+        raise ValueError("jpeg_enc_blocks: max_blocks must be positive")
+    lib.call("ssn_jpeg_enc_blocks", _p(pix), pix.numel(), _p(desc), n, int(max_blocks), _p(quant), _p(coef), coef.shape[0], _stream(lib, coef))
+
+
+def jpeg_enc_count(coef, desc, max_blocks, tables, blkbits, status):
+    """ssn_jpeg_enc_count: status int32 [images] is zeroed; blkbits int32 [blocks] (written)."""
+    lib = _check(coef, desc, tables, blkbits, status)
+    n = _jpeg_enc_common("jpeg_enc_count", desc, coef=coef, tables=tables, blkbits=blkbits, status=status)
+    if int(max_blocks) < 1:
+        raise ValueError("jpeg_enc_count: max_blocks must be positive")
+    lib.call("ssn_jpeg_enc_count", _p(coef), coef.shape[0], _p(desc), n, int(max_blocks), _p(tables), _p(blkbits), _p(status),
+             _stream(lib, coef))
+
+
+def jpeg_enc_scan(desc, blkbits, ivals, rawlen, status):
+    """ssn_jpeg_enc_scan: blkbits -> bit offsets in place; ivals int32 [intervals] and rawlen int32 [images] (written)."""
+    lib = _check(desc, blkbits, ivals, rawlen, status)
+    n = _jpeg_enc_common("jpeg_enc_scan", desc, blkbits=blkbits, ivals=ivals, rawlen=rawlen, status=status)
+    if ivals.shape[0] > blkbits.shape[0]:
+        raise ValueError("jpeg_enc_scan: more intervals than blocks")
+    lib.call("ssn_jpeg_enc_scan", _p(desc), n, _p(blkbits), blkbits.shape[0], _p(ivals), ivals.shape[0], _p(rawlen), _p(status),
+             _stream(lib, blkbits))
+
+
+def jpeg_enc_pack(coef, desc, max_blocks, tables, blkbits, ivals, rawlen, raw, status):
+    """ssn_jpeg_enc_pack: raw uint8 [bytes] is zeroed, then written."""
+    lib = _check(coef, desc, tables, blkbits, ivals, rawlen, raw, status)
+    n = _jpeg_enc_common("jpeg_enc_pack", desc, coef=coef, tables=tables, blkbits=blkbits, ivals=ivals, rawlen=rawlen, status=status, raw=raw)
+    if int(max_blocks) < 1:
+        raise ValueError("jpeg_enc_pack: max_blocks must be positive")
+    lib.call("ssn_jpeg_enc_pack", _p(coef), coef.shape[0], _p(desc), n, int(max_blocks), _p(tables), _p(blkbits), _p(ivals), ivals.shape[0],
+             _p(rawlen), _p(raw), raw.numel(), _p(status), _stream(lib, raw))
+
+
+def jpeg_enc_assemble(raw, desc, ivals, rawlen, headers, ffcount, data, offsets, lengths, status):
+    """ssn_jpeg_enc_assemble: headers uint8 [bytes]; ffcount int32 [images] (scratch); data uint8 [bytes], offsets int64 [images] and
+    lengths int32 [images] (written)."""
+    lib = _check(raw, desc, ivals, rawlen, headers, ffcount, data, offsets, lengths, status)
+    n = _jpeg_enc_common("jpeg_enc_assemble", desc, ivals=ivals, rawlen=rawlen, status=status, raw=raw)
+    if headers.dtype != torch.uint8 or headers.dim() != 1 or headers.numel() < 1:
+        raise ValueError("jpeg_enc_assemble: headers must be uint8 [bytes]")
+    if data.dtype != torch.uint8 or data.dim() != 1 or data.numel() < 1:
+        raise ValueError("jpeg_enc_assemble: data must be uint8 [bytes]")
+    if offsets.dtype != torch.int64 or tuple(offsets.shape) != (n,):
+        raise ValueError("jpeg_enc_assemble: offsets must be int64 [images]")
+    for name, t in (("ffcount", ffcount), ("lengths", lengths)):
+        if t.dtype != torch.int32 or tuple(t.shape) != (n,):
+            raise ValueError("jpeg_enc_assemble: %s must be int32 [images]" % name)
+    lib.call("ssn_jpeg_enc_assemble", _p(raw), raw.numel(), _p(desc), n, _p(ivals), ivals.shape[0], _p(rawlen), _p(headers), headers.numel(),
+             _p(ffcount), _p(data), data.numel(), _p(offsets), _p(lengths), _p(status), _stream(lib, data))

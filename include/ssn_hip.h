@@ -750,6 +750,33 @@ int ssn_jpeg_idct(const short* coef, long total_blocks, const int* desc, int n_i
 int ssn_jpeg_pixels(const unsigned char* planes, long plane_bytes, const int* desc, int n_images, long max_pixels, int out_c,
                     unsigned char* out, long out_bytes, hipStream_t stream);
 
+/* Baseline JPEG encoding of a batch of images (csrc/jpeg_encode.hip): the bytes PIL's Image.save(f, "JPEG", quality=, subsampling=,
+ * restart_marker_blocks=) writes, byte for byte, for the libjpeg PIL links.  The host (jpeg_encode.py) describes
+ * the batch in desc int32 [images][desc_ints] and prepares the quantisation tables (uint16 [2][64], natural order), the Huffman code
+ * tables (uint32 [4][256]: DC luma, AC luma, DC chroma, AC chroma, entry = length << 16 | code) and the header bytes of every file.
+ *  blocks    colour conversion, edge expansion, downsampling, islow forward DCT, quantisation: pix uint8 ([H][W] or [H][W][3] per image
+ *            at its offset) -> coef int16 [total_blocks][64], zigzag order, rows in the scan's MCU order, dummy blocks included.
+ *  count     zero-fills status, then blkbits int32 [total_blocks]: the bits the Huffman codes of every block take.
+ *  scan      blkbits -> the bit offset of every block in its restart interval; ivals int32 [total_intervals] -> the byte offset of every
+ *            interval in its image's raw region; rawlen int32 [images] (0, and status bit 1, for an image past its raw capacity).
+ *  pack      zero-fills raw [raw_bytes], then every block ORs its codes in at its bit offset; intervals end padded with 1-bits.
+ *  assemble  ffcount int32 [images] (scratch), then lengths int32 / offsets int64 [images] and the files in data: header, scan with 00
+ *            after every FF and RSTn between intervals, FFD9.  A file longer than its capacity gets length 0 and status bit 1.
+ * status bits: 1 the file does not fit, 2 a coefficient the tables have no code for, 4 an unusable desc row. */
+int ssn_jpeg_enc_layout(int* desc_ints, int* block_bits);
+int ssn_jpeg_enc_blocks(const unsigned char* pix, long pix_bytes, const int* desc, int n_images, int max_blocks,
+                        const unsigned short* quant, short* coef, long total_blocks, hipStream_t stream);
+int ssn_jpeg_enc_count(const short* coef, long total_blocks, const int* desc, int n_images, int max_blocks, const unsigned int* tables,
+                       int* blkbits, int* status, hipStream_t stream);
+int ssn_jpeg_enc_scan(const int* desc, int n_images, int* blkbits, long total_blocks, int* ivals, long total_intervals, int* rawlen,
+                      int* status, hipStream_t stream);
+int ssn_jpeg_enc_pack(const short* coef, long total_blocks, const int* desc, int n_images, int max_blocks, const unsigned int* tables,
+                      const int* blkbits, const int* ivals, long total_intervals, const int* rawlen, unsigned char* raw, long raw_bytes,
+                      int* status, hipStream_t stream);
+int ssn_jpeg_enc_assemble(const unsigned char* raw, long raw_bytes, const int* desc, int n_images, const int* ivals, long total_intervals,
+                          const int* rawlen, const unsigned char* headers, long header_bytes, int* ffcount, unsigned char* data,
+                          long data_bytes, long* offsets, int* lengths, int* status, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

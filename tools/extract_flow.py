@@ -5,7 +5,8 @@ this project (the reference hands it to dense_flow, i.e. OpenCV's CUDA TV-L1).
 Every directory under SRC_ROOT that holds ``img_00001.jpg, img_00002.jpg, ...`` is one video; for each of them
 ``OUT_ROOT/<video>/<flow-prefix>x_%05d.jpg`` and ``<flow-prefix>y_%05d.jpg`` are written, number i holding the flow from frame i to
 frame i + 1 quantised as dense_flow does (``--bound``) -- the files ``FrameDirReader(modality="Flow")`` and the reference's data
-sets read.  The frames of a video go to the GPU once; the flow comes back as uint8.
+sets read.  The frames of a video go to the GPU once; the flow comes back as uint8, or with ``--gpu-encode`` as the finished files
+(the same bytes; ``--restart-blocks K`` adds restart markers the device decoder splits at).
 
     python tools/extract_flow.py /data/frames /data/flow --bound 20 --flow-prefix flow_
 
@@ -63,6 +64,18 @@ def write_flow(folder, prefix, flow_u8, quality):
             Image.fromarray(flow_u8[i, c]).save(os.path.join(folder, "{}{}_{:05d}.jpg".format(prefix, axis, i + 1)), quality=quality)
 
 
+def write_flow_on_device(folder, prefix, flow_u8, quality, encoder, restart_blocks=0):
+    """The same files from a flow that stays on the device (--gpu-encode): uint8 [T-1, 2, H, W] is compressed there
+    (jpeg_encode.JpegEncoder) and only the files' bytes come down."""
+    os.makedirs(folder, exist_ok=True)
+    pairs, _, h, w = flow_u8.shape
+    files = encoder.encode(flow_u8.reshape(pairs * 2, h, w), quality=quality, restart_blocks=restart_blocks)
+    for i in range(pairs):
+        for c, axis in enumerate("xy"):
+            with open(os.path.join(folder, "{}{}_{:05d}.jpg".format(prefix, axis, i + 1)), "wb") as f:
+                f.write(files[2 * i + c])
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("src_root")
@@ -73,6 +86,10 @@ def main(argv=None):
     ap.add_argument("--iterations", type=int, default=300)
     ap.add_argument("--jpeg-quality", type=int, default=95)
     ap.add_argument("--gpu-decode", action="store_true", help="decode the input frames on the device (jpeg_decode.JpegDecoder)")
+    ap.add_argument("--gpu-encode", action="store_true",
+                    help="compress the flow images on the device (jpeg_encode.JpegEncoder): the same bytes, without PIL")
+    ap.add_argument("--restart-blocks", type=int, default=0,
+                    help="with --gpu-encode: restart markers every K MCUs (PIL's restart_marker_blocks=K); the decoder splits at them")
     ap.add_argument("--quiet", action="store_true")
     args = ap.parse_args(argv)
 
@@ -85,6 +102,12 @@ def main(argv=None):
     if args.gpu_decode:
         from action_detection_amd.jpeg_decode import JpegDecoder
         decoder = JpegDecoder(dev)
+    if args.restart_blocks and not args.gpu_encode:
+        ap.error("--restart-blocks needs --gpu-encode")
+    encoder = None
+    if args.gpu_encode:
+        from action_detection_amd.jpeg_encode import JpegEncoder
+        encoder = JpegEncoder(dev)
     videos = video_dirs(args.src_root)
     if not videos:
         print("no directory with img_00001.jpg, img_00002.jpg, ... under %s" % args.src_root, file=sys.stderr)
@@ -94,8 +117,11 @@ def main(argv=None):
             frames = load_frames_on_device(os.path.join(args.src_root, rel), n, decoder)
         else:
             frames = torch.from_numpy(load_frames(os.path.join(args.src_root, rel), n)).to(dev)
-        flow = extractor.extract(frames).cpu().numpy()
-        write_flow(os.path.join(args.out_root, rel), args.flow_prefix, flow, args.jpeg_quality)
+        flow = extractor.extract(frames)
+        if encoder is not None:
+            write_flow_on_device(os.path.join(args.out_root, rel), args.flow_prefix, flow, args.jpeg_quality, encoder, args.restart_blocks)
+        else:
+            write_flow(os.path.join(args.out_root, rel), args.flow_prefix, flow.cpu().numpy(), args.jpeg_quality)
         if not args.quiet:
             print("%s: %d frames -> %d flow pairs" % (rel, n, flow.shape[0]))
     return 0
