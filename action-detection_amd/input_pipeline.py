@@ -4,8 +4,9 @@
 ToTorchFormatTensor(div=False) -> GroupNormalize(mean, std)`` (``ssn_train.py:106-111`` the same tail behind a
 random crop + flip) and runs it image by image in PIL on the loader workers.  Here the decoded, scaled frames go
 to the GPU as uint8 and one launch (``ssn_frames_crop_normalize``) produces the network input in the layout
-``SSN.forward`` / ``DenseTester`` expect (crop-major ``[crop][tick]`` rows).  Decoding and PIL's antialiased resize
-stay on the CPU side (not arithmetic of this repo's path).
+``SSN.forward`` / ``DenseTester`` expect (crop-major ``[crop][tick]`` rows).  The test-time ``GroupScale`` in front of the crops
+(PIL's bilinear resize of the whole frame) is ``GpuFrameTransform.scale`` (``ssn_frames_scale``, bit-identical to Pillow);
+decoding is ``jpeg_decode.JpegDecoder``.
 """
 import torch
 
@@ -21,6 +22,16 @@ def fill_fix_offset(more_fix_crop, image_w, image_h, crop_w, crop_h):
         ret += [(0, 2 * h_step), (4 * w_step, 2 * h_step), (2 * w_step, 4 * h_step), (2 * w_step, 0 * h_step),
                 (1 * w_step, 1 * h_step), (3 * w_step, 1 * h_step), (1 * w_step, 3 * h_step), (3 * w_step, 3 * h_step)]
     return ret
+
+
+def scaled_size(w, h, size):
+    """-> (w', h') of ``GroupScale(size)`` (transforms.GroupScale._one): the short side becomes ``size``, the long one
+    ``int(size * long / short)``; unchanged when the short side is ``size`` already."""
+    if (w <= h and w == size) or (h <= w and h == size):
+        return w, h
+    if w < h:
+        return size, int(size * h / w)
+    return int(size * w / h), size
 
 
 class GpuFrameTransform(object):
@@ -44,14 +55,40 @@ class GpuFrameTransform(object):
         K.frames_crop_normalize(frames, out, crops, self.roll, self.is_flow, self.mean, self.std)
         return out
 
-    def oversample(self, frames):
+    def scale(self, frames, size):
+        """``GroupScale(size)`` on the device: uint8 [n, H, W, C] -> uint8 [n, H', W', C] (``scaled_size``), PIL's bilinear resize bit
+        for bit.  The input itself (no launch) when the short side is ``size`` already; ValueError when the frames would shrink by
+        more than 6 (the kernel's taps) -- such frames take the host chain."""
+        if frames.dtype != torch.uint8 or frames.dim() != 4:
+            raise ValueError("frames: uint8 [n_img, H, W, C] as decoded")
+        h, w = frames.shape[1], frames.shape[2]
+        ow, oh = scaled_size(w, h, int(size))
+        if (ow, oh) == (w, h):
+            return frames
+        if not K.frames_scale_supported(h, w, oh, ow):      # (short side <= 6 x size, long side within the kernel's taps)
+            raise ValueError("GroupScale(%d) of %d x %d frames shrinks by more than %d" % (size, w, h, K.FRAMES_SCALE_MAX_RATIO))
+        return K.frames_scale(frames.to(self.mean.device), (oh, ow))
+
+    def oversample(self, frames, scale_size=None):
         """GroupOverSample: 5 fixed crops x {as is, flipped} -> [10 * n_img * C, crop_h, crop_w], the tensor
-        ``ssn_dataset.get_test_data`` yields per frame batch (view it as (-1, length, H, W))."""
+        ``ssn_dataset.get_test_data`` yields per frame batch (view it as (-1, length, H, W)).  ``scale_size``:
+        ``GroupOverSample(crop, scale_size)`` -- the frames go through ``scale`` first (flow: the inversion under a flip applies to
+        the scaled pixels); None: the frames are cropped as they are."""
+        if scale_size is not None:
+            frames = self.scale(frames, scale_size)
         offs = fill_fix_offset(False, frames.shape[2], frames.shape[1], self.crop_w, self.crop_h)
         crops = []
         for ow, oh in offs:
             crops += [(ow, oh, 0), (ow, oh, 1)]
         return self._run(frames, crops).reshape(-1, self.crop_h, self.crop_w)
+
+    def center_crop(self, frames, scale_size=None):
+        """``GroupScale(scale_size)`` -> ``GroupCenterCrop(crop)`` -> the tail: the 1-crop chain of ssn_test.py:107-111
+        -> [n_img * C, crop_h, crop_w]."""
+        if scale_size is not None:
+            frames = self.scale(frames, scale_size)
+        h, w = frames.shape[1], frames.shape[2]
+        return self.crop(frames, int(round((w - self.crop_w) / 2.)), int(round((h - self.crop_h) / 2.)), False)
 
     def crop(self, frames, off_w, off_h, flip):
         """One crop (+ optional flip) of every frame: the tail of the training chain -> [n_img * C, crop_h, crop_w]."""

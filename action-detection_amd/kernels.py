@@ -774,6 +774,38 @@ def frames_crop_resize_normalize(src, boxes, flips, out_hw, roll, invert_even, m
     return dst
 
 
+FRAMES_SCALE_MAX_RATIO = 6      # csrc/frames.hip: 13 taps per axis
+
+
+def frames_scale_supported(hs, ws, oh, ow):
+    """What ssn_frames_scale takes: the axis with the smaller in / out ratio (the side GroupScale sets) shrinks by at most 6; the other
+    one, whose length GroupScale truncates to an integer, stays below the 13-tap capacity (ratio 6.5)."""
+    r = FRAMES_SCALE_MAX_RATIO
+    return (hs <= r * oh or ws <= r * ow) and 2 * hs < (2 * r + 1) * oh and 2 * ws < (2 * r + 1) * ow
+
+
+def frames_scale(src, out_hw, dst=None):
+    """GroupScale's resize of whole frames (ssn_frames_scale): src uint8 [n_img, Hs, Ws, C], C = 1 or 3, -> uint8 [n_img, out_h, out_w, C],
+    bit-identical to ``img.resize((out_w, out_h), Image.BILINEAR)``.  ValueError (nothing launched) beyond the kernel's ratio of 6."""
+    if src.dtype != torch.uint8 or src.dim() != 4:
+        raise ValueError("frames_scale: uint8 [n_img, H, W, C]")
+    src = src.contiguous()
+    lib = _check(src)
+    n_img, hs, ws, c = src.shape
+    oh, ow = int(out_hw[0]), int(out_hw[1])
+    if oh < 1 or ow < 1:
+        raise ValueError("frames_scale: empty output %d x %d" % (ow, oh))
+    if not frames_scale_supported(hs, ws, oh, ow):
+        raise ValueError("frames_scale: %d x %d -> %d x %d shrinks by more than %d" % (ws, hs, ow, oh, FRAMES_SCALE_MAX_RATIO))
+    if dst is None:
+        dst = torch.empty((n_img, oh, ow, c), device=src.device, dtype=torch.uint8)
+    assert dst.dtype == torch.uint8 and tuple(dst.shape) == (n_img, oh, ow, c) and dst.is_contiguous() and dst.device == src.device
+    ws_bytes = int(lib.cdll.ssn_frames_scale_workspace_bytes(oh, ow))
+    wsp = torch.empty(ws_bytes // 4, device=src.device, dtype=torch.int32)
+    lib.call("ssn_frames_scale", _p(src), _p(dst), n_img, hs, ws, c, oh, ow, _p(wsp), ws_bytes, _stream(lib, src))
+    return dst
+
+
 def frame_diff(x, new_length, channels=3):
     """RGBDiff input (SSN._get_diff): x [..., (new_length + 1) * channels * k, H, W] stacked frames per segment ->
     [n_segments, new_length * channels, H, W] differences of consecutive frames."""

@@ -343,6 +343,15 @@ size_t ssn_frames_resize_workspace_bytes(int n_img, int out_h, int out_w);
 int ssn_frames_crop_resize_normalize(const unsigned char* src, float* dst, int n_img, int Hs, int Ws, int C, int out_h, int out_w,
                                      const int* box, const int* flip, int roll, int invert_even, const float* mean, int n_mean,
                                      const float* stdv, int n_std, void* workspace, size_t workspace_bytes, hipStream_t stream);
+/* The TEST-time GroupScale on the GPU (transforms.py:83-96; inside GroupOverSample :103-132 and in front of GroupCenterCrop,
+ * ssn_test.py:107-115): Pillow's 8-bit BILINEAR resize of whole frames, bit-identical to img.resize((out_w, out_h), Image.BILINEAR).
+ * src [n_img][Hs][Ws][C] uint8 -> dst [n_img][out_h][out_w][C] uint8, C = 1 or 3; the images of a call share one size (the frames of
+ * one video), so there is one coefficient table per call.  Up to 13 taps per axis: the axis with the smaller in / out ratio (the
+ * side GroupScale sets) may shrink by up to 6, the other one (its length is truncated to an integer) by less than 6.5.
+ * workspace: ssn_frames_scale_workspace_bytes() device bytes, 4-byte aligned.  Two launches on `stream`, no allocation, no host read. */
+size_t ssn_frames_scale_workspace_bytes(int out_h, int out_w);
+int ssn_frames_scale(const unsigned char* src, unsigned char* dst, int n_img, int Hs, int Ws, int C, int out_h, int out_w,
+                     void* workspace, size_t workspace_bytes, hipStream_t stream);
 
 /* Detection post-processing of one video (csrc/detect.hip): score fusion softmax(activity)[1:] * exp(completeness),
  * top-k over all (proposal, class) pairs, temporal NMS per class and location regression

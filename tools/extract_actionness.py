@@ -60,11 +60,13 @@ def file_reader(frame_root, modality, flow_pref=""):
     return read
 
 
-def device_transform(net, modality, device, input_size=None):
+def device_transform(net, modality, device, input_size=None, scale=False):
     """--gpu-decode: [bytes] -> what ``transform(frames)`` of ``extract`` yields for 10 crops, with the files decoded on the device
     (jpeg_decode.JpegDecoder) and GroupOverSample -> Stack -> ToTorchFormatTensor -> GroupNormalize as one launch
     (input_pipeline.GpuFrameTransform).  GroupOverSample's GroupScale(scale_size) is the identity on frames whose short side is
-    scale_size already -- the 340 x 256 frames the extraction scripts write; other sizes are refused."""
+    scale_size already -- the 340 x 256 frames the extraction scripts write; other sizes are refused unless ``scale`` (--gpu-scale)
+    is set: then GroupScale runs on the device too (``GpuFrameTransform.scale``; Inception-v3's scale_size is 341, so its frames
+    always need it)."""
     from action_detection_amd.input_pipeline import GpuFrameTransform
     from action_detection_amd.jpeg_decode import JpegDecoder
     decoder = JpegDecoder(device)
@@ -73,6 +75,8 @@ def device_transform(net, modality, device, input_size=None):
 
     def transform(blobs):
         frames = decoder.decode(blobs, "RGB" if modality == "RGB" else "L", stack=True)
+        if scale:
+            return tf.oversample(frames, scale_size=net.scale_size)
         if min(frames.shape[1], frames.shape[2]) != net.scale_size:
             raise ValueError("--gpu-decode needs frames whose short side is %d, got %d x %d" % (net.scale_size, frames.shape[2], frames.shape[1]))
         return tf.oversample(frames)
@@ -130,6 +134,7 @@ def main(argv=None):
     ap.add_argument("--grouping", type=str, default="reference", choices=["reference", "tick"])
     ap.add_argument("--device", type=str, default="cuda:0")
     ap.add_argument("--gpu-decode", action="store_true", help="decode the frames on the device (10 crops, frames at scale_size)")
+    ap.add_argument("--gpu-scale", action="store_true", help="with --gpu-decode: frames of any size, GroupScale on the device")
     args = ap.parse_args(argv)
 
     import torch
@@ -148,7 +153,7 @@ def main(argv=None):
     if args.gpu_decode:
         scores = extract(net, sampler, file_reader(args.frame_root, args.modality, args.flow_pref), args.test_crops, args.input_size,
                          args.tick_batch, args.grouping, args.max_num,
-                         transform=device_transform(net, args.modality, args.device, args.input_size))
+                         transform=device_transform(net, args.modality, args.device, args.input_size, scale=args.gpu_scale))
     else:
         scores = extract(net, sampler, pil_loader(args.frame_root, args.modality, args.flow_pref), args.test_crops, args.input_size,
                          args.tick_batch, args.grouping, args.max_num)
