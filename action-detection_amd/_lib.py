@@ -19,7 +19,7 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(_HERE, "libssn_hip.so")
-SOURCES = ["conv_igemm.hip", "conv_x6.hip", "conv_x6_rect.hip", "conv_wgrad.hip", "conv_wgrad_x6.hip", "elementwise.hip", "bn_train.hip", "frames.hip", "detect.hip", "pool.hip", "stpp.hip", "heads_losses.hip", "conv_pl.hip", "planes_ops.hip", "planes_bn.hip", "wgrad_pl.hip", "tag.hip", "eval.hip", "actionness.hip", "train_step.hip", "flow.hip", "jpeg.hip", "jpeg_encode.hip"]
+SOURCES = ["conv_igemm.hip", "conv_x6.hip", "conv_x6_rect.hip", "conv_wgrad.hip", "conv_wgrad_x6.hip", "elementwise.hip", "bn_train.hip", "frames.hip", "detect.hip", "pool.hip", "stpp.hip", "heads_losses.hip", "conv_pl.hip", "planes_ops.hip", "planes_bn.hip", "wgrad_pl.hip", "tag.hip", "eval.hip", "actionness.hip", "train_step.hip", "flow.hip", "jpeg.hip", "jpeg_encode.hip", "jpeg_transcode.hip"]
 
 STPP_MAX_PARTS = 24
 
@@ -98,6 +98,8 @@ _SIGS = {
     "ssn_jpeg_enc_scan": "piplplppp",
     "ssn_jpeg_enc_pack": "plpiippplpplpp",
     "ssn_jpeg_enc_assemble": "plpiplpplpplpppp",
+    "ssn_jpeg_transcode_layout": "p",
+    "ssn_jpeg_transcode_blocks": "plpiiplpp",
     "ssn_frames_crop_normalize": "ppiiiiiiipppiipipip",
     "ssn_frames_crop_resize_normalize": "ppiiiiiippiipipipup",
     "ssn_frames_scale": "ppiiiiiipup",

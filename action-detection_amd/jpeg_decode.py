@@ -304,6 +304,22 @@ def _align(n, a=16):
     return -(-n // a) * a
 
 
+class CoefficientBatch(object):
+    """What ``JpegDecoder.coefficients`` returns.  ``headers``: the ``JpegHeader`` of every file (``supported`` False: the file has no
+    coefficients here).  ``coef``: int16 [blocks, 64] on the device, natural order, absolute DC; the blocks of file i are rows
+    ``rows[i, 7]`` .. ``+ rows[i, 8]``, planar: luma in raster order over the padded MCU grid, then Cb, then Cr.  ``desc``: the
+    decoder's descriptor rows on the device, ``rows`` the same on the host.  ``status``: int32 [files] on the device, non-zero for a
+    damaged scan (``JpegDecoder``).  ``coef``, ``desc`` and ``rows`` are None if no file is supported."""
+
+    def __init__(self, headers, coef, desc, status, max_blocks, rows=None):
+        self.headers, self.coef, self.desc, self.status, self.max_blocks, self.rows = headers, coef, desc, status, max_blocks, rows
+
+    def blocks(self, i):
+        """The coefficients of file i: int16 [its blocks, 64] (a view)."""
+        off, n = int(self.rows[i, 7]), int(self.rows[i, 8])
+        return self.coef[off:off + n]
+
+
 class JpegDecoder(object):
     """``decode(blobs, mode)``: the files' pixels as device tensors, uint8 [H, W, 3] ("RGB") or [H, W, 1] ("L") each -- what
     ``np.asarray(Image.open(f).convert(mode))`` holds.  Everything is enqueued on the current stream of ``device``; nothing is
@@ -480,6 +496,34 @@ class JpegDecoder(object):
         if stack:
             return out.view(n, shapes[0][0], shapes[0][1], out_c)
         return views
+
+    def coefficients(self, blobs):
+        """The marker walk, the upload and the entropy launch of ``decode`` and nothing after them -> ``CoefficientBatch``: the
+        quantised coefficients of the files as the entropy stage leaves them (the launch zero-fills the buffer first: it writes the
+        non-zero coefficients only).  What lossless transcoding starts from (jpeg_transcode.py).  Nothing is read back."""
+        blobs = [bytes(b) for b in blobs]
+        if not blobs:
+            raise ValueError("JpegDecoder: no files")
+        parsed = [parse_jpeg(blob) for blob in blobs]
+        headers = [h if h.supported else None for h in parsed]
+        n = len(blobs)
+        self._out_off = [0] * (n + 1)      # (no pixels: the rows' output offsets are not used)
+        self.status = torch.zeros(n, dtype=torch.int32, device=self.device)
+        self.uploaded_bytes = 0
+        self._last = None
+        if all(h is None for h in headers):
+            return CoefficientBatch(parsed, None, None, self.status, 0)
+        staging, offs, sz = self._plan(blobs, headers, 1)
+        self.uploaded_bytes = staging.size
+        dev = self._timed("upload", self._upload, staging)
+        bits = dev[offs[0]:offs[0] + sz["bits"]]
+        desc = dev[offs[1]:offs[1] + n * self.desc_ints * 4].view(torch.int32).view(n, self.desc_ints)
+        units = dev[offs[2]:offs[2] + sz["units"] * self.unit_ints * 4].view(torch.int32).view(-1, self.unit_ints)
+        tables = dev[offs[3]:offs[3] + sz["sets"] * 16 * self.table_words].view(torch.int32).view(-1, 4, self.table_words)
+        coef = self._alloc((sz["blocks"], 64), torch.int16)
+        self._timed("entropy", K.jpeg_entropy, bits, desc, units, tables, coef, self.status)
+        rows = np.frombuffer(staging, np.int32, n * self.desc_ints, offs[1]).reshape(n, self.desc_ints)
+        return CoefficientBatch(parsed, coef, desc, self.status, sz["max_blocks"], rows)
 
     def check(self):
         """Read ``status`` (a host synchronisation) and decode the damaged files of the last batch with PIL, in place.

@@ -188,22 +188,29 @@ class JpegEncoder(object):
         return views, views[0].shape[-1], (stacked.reshape(-1) if stacked is not None else None)
 
     def _plan(self, shapes, ncomp, hs, vs, quality, restart_blocks, capacity):
-        n = len(shapes)
-        desc = np.zeros((n, self.desc_ints), np.int64)
         qtabs = quant_tables(quality)
+        return self._plan_specs([(h, w, ncomp, hs, vs, qtabs, restart_blocks) for (h, w) in shapes], qtabs, capacity)
+
+    def _plan_specs(self, specs, quant, capacity, pixels=True):
+        """specs: per image (height, width, components, luma hs, vs, [luma, chroma] quantisation tables for its header, restart
+        interval in MCUs or 0).  quant: the two tables the first stage divides by (not looked at when coefficients are given).  pixels=False:
+        there are none (the rows' pixel offsets stay 0 and do not count against the 2 GiB)."""
+        n = len(specs)
+        desc = np.zeros((n, self.desc_ints), np.int64)
         headers, cache = [], {}
         pix_off = blk_off = int_off = raw_off = hdr_off = out_total = max_blocks = 0
-        bpm = 1 if ncomp == 1 else hs * vs + 2
-        for i, (h, w) in enumerate(shapes):
+        for i, (h, w, ncomp, hs, vs, qtabs, restart_blocks) in enumerate(specs):
+            bpm = 1 if ncomp == 1 else hs * vs + 2
             mx, my = -(-w // (8 * hs)), -(-h // (8 * vs))
             nblocks = mx * my * bpm
             if nblocks * self.block_bits >= (1 << 31):
                 raise ValueError("JpegEncoder: a %d x %d image is too large (its scan may pass 2^31 bits)" % (w, h))
             ri = min(restart_blocks, mx * my) if restart_blocks else mx * my
             nint = -(-(mx * my) // ri)
-            if (h, w) not in cache:
-                cache[(h, w)] = header_bytes(w, h, ncomp, hs, vs, qtabs, restart_blocks)
-            hdr = cache[(h, w)]
+            key = (h, w, ncomp, hs, vs, restart_blocks, qtabs[0].tobytes(), qtabs[-1].tobytes())
+            if key not in cache:
+                cache[key] = header_bytes(w, h, ncomp, hs, vs, qtabs, restart_blocks)
+            hdr = cache[key]
             # the worst case: every block takes block_bytes, every byte of the scan is an FF (DESIGN.md 3.11)
             raw_worst = self.block_bytes * nblocks
             out_worst = len(hdr) + 2 * raw_worst + 2 * (nint - 1) + 2
@@ -212,7 +219,7 @@ class JpegEncoder(object):
             desc[i, :18] = (w, h, ncomp, hs, vs, mx, my, pix_off, blk_off, nblocks, ri, int_off, nint, raw_off, raw_cap, hdr_off, len(hdr),
                             out_cap)
             headers.append(hdr)
-            pix_off += h * w * ncomp
+            pix_off += h * w * ncomp if pixels else 0
             blk_off += nblocks
             int_off += nint
             raw_off += raw_cap
@@ -222,6 +229,7 @@ class JpegEncoder(object):
         if blk_off >= (1 << 25) or pix_off >= (1 << 31) or raw_off >= (1 << 31) or n > 65535:
             raise ValueError("JpegEncoder: the batch is too large for one call (65535 images, 2^25 blocks, 2 GiB of pixels or of scans); "
                              "split it or give a capacity")
+        qtabs = quant
         sections = [desc.astype(np.int32).view(np.uint8).reshape(-1), np.stack(qtabs).astype(np.int16).view(np.uint8).reshape(-1),
                     np.frombuffer(b"".join(headers), np.uint8)]
         offs, total = [], 0
@@ -267,6 +275,36 @@ class JpegEncoder(object):
         if flat is None:
             flat = torch.cat([v.reshape(-1) for v in views]) if len(views) > 1 else views[0].reshape(-1)
         return self._run(flat, staging, offs, sz, len(views), as_bytes)
+
+    def plan_coefficients(self, specs, capacity=None):
+        """The tables of a batch whose coefficients exist already (lossless transcoding, jpeg_transcode.py).  specs: per image
+        ``(height, width, components, hs, vs, [luma, chroma] uint16 [64] natural-order tables, restart interval)``; images of one
+        batch may differ in all of them.  The header of every file carries the given tables and, with a restart interval k > 0, a DRI
+        segment of k; the Huffman tables are the standard ones.  -> a plan for ``encode_coefficients``; ``plan["desc"]`` (host, int64
+        [images, desc_ints]) says where the coefficients of every image go: its blocks are rows ``desc[i, 8]`` .. ``+ desc[i, 9]``."""
+        specs = list(specs)
+        if not specs:
+            raise ValueError("JpegEncoder: no images")
+        for (h, w, ncomp, hs, vs, qtabs, restart) in specs:
+            if ncomp not in (1, 3) or (hs, vs) not in _SAMPLING.values() or (ncomp == 1 and (hs, vs) != (1, 1)):
+                raise ValueError("JpegEncoder: gray, or 3 components with luma sampling 1x1, 2x1 or 2x2")
+            if not (1 <= h <= 65535 and 1 <= w <= 65535):
+                raise ValueError("JpegEncoder: image sizes are 1 .. 65535, got %d x %d" % (w, h))
+            if not 0 <= restart <= 65535:
+                raise ValueError("JpegEncoder: restart_blocks is 0 (none) .. 65535 MCUs")
+            if len(qtabs) < (1 if ncomp == 1 else 2) or any(np.asarray(q).shape != (64,) or np.asarray(q).min() < 1 or
+                                                             np.asarray(q).max() > 255 for q in qtabs):
+                raise ValueError("JpegEncoder: quantisation tables are [64] entries of 1 .. 255 (8-bit tables)")
+        staging, offs, sz = self._plan_specs(specs, quant_tables(50), capacity, pixels=False)
+        desc = np.frombuffer(staging, np.int32, len(specs) * self.desc_ints, offs[0]).reshape(len(specs), self.desc_ints).astype(np.int64)
+        return dict(staging=staging, offs=offs, sizes=sz, n=len(specs), desc=desc)
+
+    def encode_coefficients(self, plan, coef, as_bytes=True):
+        """The count, scan, pack and assemble stages on given coefficients: coef int16 [plan["sizes"]["blocks"], 64] on the device,
+        zigzag order, rows in scan order (what the first stage would have written)."""
+        if coef.dtype != torch.int16 or tuple(coef.shape) != (plan["sizes"]["blocks"], 64):
+            raise ValueError("JpegEncoder: coef must be int16 [%d, 64]" % plan["sizes"]["blocks"])
+        return self._run(None, plan["staging"], plan["offs"], plan["sizes"], plan["n"], as_bytes, coef=coef)
 
     def _run(self, flat, staging, offs, sz, n, as_bytes, coef=None):
         """The launches.  coef: coefficients to code instead of the ones the first stage computes (the stage-level tests)."""

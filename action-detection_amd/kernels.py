@@ -1579,3 +1579,33 @@ def jpeg_enc_assemble(raw, desc, ivals, rawlen, headers, ffcount, data, offsets,
             raise ValueError("jpeg_enc_assemble: %s must be int32 [images]" % name)
     lib.call("ssn_jpeg_enc_assemble", _p(raw), raw.numel(), _p(desc), n, _p(ivals), ivals.shape[0], _p(rawlen), _p(headers), headers.numel(),
              _p(ffcount), _p(data), data.numel(), _p(offsets), _p(lengths), _p(status), _stream(lib, data))
+
+
+# ------------------------------------------------------------------------------------ lossless JPEG transcoding (csrc/jpeg_transcode.hip)
+def jpeg_transcode_layout():
+    """ints of a desc row jpeg_transcode.py builds: ncomp, hs, vs, mcux, mcuy, first source block, first destination block, blocks."""
+    lib = _lib.get_lib()
+    v = ctypes.c_int()
+    lib.call("ssn_jpeg_transcode_layout", ctypes.byref(v))
+    return v.value
+
+
+def jpeg_transcode_blocks(src, desc, max_blocks, dst, status):
+    """ssn_jpeg_transcode_blocks: src int16 [blocks, 64] (what jpeg_entropy writes: natural order, planar blocks); dst int16
+    [blocks, 64] (written: what jpeg_enc_count reads: zigzag order, blocks in scan order); status int32 [images] is zeroed, bit 4 marks
+    an unusable desc row."""
+    lib = _check(src, desc, dst, status)
+    ints = jpeg_transcode_layout()
+    if desc.dtype != torch.int32 or desc.dim() != 2 or desc.shape[1] != ints or not 1 <= desc.shape[0] <= 65535:
+        raise ValueError("jpeg_transcode_blocks: desc must be int32 [images, %d], 1 .. 65535 images" % ints)
+    for name, t in (("src", src), ("dst", dst)):
+        if t.dtype != torch.int16 or t.dim() != 2 or t.shape[1] != 64 or not 1 <= t.shape[0] < (1 << 25) or t.data_ptr() % 16:
+            raise ValueError("jpeg_transcode_blocks: %s must be int16 [blocks, 64], fewer than 2^25 blocks, 16-byte aligned" % name)
+    if src.data_ptr() == dst.data_ptr():
+        raise ValueError("jpeg_transcode_blocks: src and dst must be different buffers")
+    if status.dtype != torch.int32 or tuple(status.shape) != (desc.shape[0],):
+        raise ValueError("jpeg_transcode_blocks: status must be int32 [images]")
+    if int(max_blocks) < 1:
+        raise ValueError("jpeg_transcode_blocks: max_blocks must be positive")
+    lib.call("ssn_jpeg_transcode_blocks", _p(src), src.shape[0], _p(desc), desc.shape[0], int(max_blocks), _p(dst), dst.shape[0],
+             _p(status), _stream(lib, dst))

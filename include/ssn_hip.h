@@ -786,6 +786,18 @@ int ssn_jpeg_enc_assemble(const unsigned char* raw, long raw_bytes, const int* d
                           const int* rawlen, const unsigned char* headers, long header_bytes, int* ffcount, unsigned char* data,
                           long data_bytes, long* offsets, int* lengths, int* status, hipStream_t stream);
 
+/* Lossless JPEG transcoding (csrc/jpeg_transcode.hip): the step between ssn_jpeg_entropy and ssn_jpeg_enc_count that jpegtran does on
+ * the host between its reader and its writer.  desc int32 [images][desc_ints]: ncomp, hs, vs, mcux, mcuy, first source block, first
+ * destination block, blocks.
+ *  layout    ints of a desc row.
+ *  blocks    zero-fills status int32 [images], then src int16 [src_blocks][64] (natural order, blocks planar per image: luma raster
+ *            over the padded MCU grid, Cb, Cr) -> dst int16 [dst_blocks][64] (zigzag order, blocks in scan order, dummy blocks
+ *            included).  Values are copied, never changed.  A row that is inconsistent or reaches past either buffer sets status bit 4
+ *            (the encoder's "unusable desc row") and writes nothing.  Both buffers 16-byte aligned. */
+int ssn_jpeg_transcode_layout(int* desc_ints);
+int ssn_jpeg_transcode_blocks(const short* src, long src_blocks, const int* desc, int n_images, int max_blocks, short* dst,
+                              long dst_blocks, int* status, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

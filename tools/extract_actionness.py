@@ -133,7 +133,8 @@ def main(argv=None):
     ap.add_argument("--tick_batch", type=int, default=32)
     ap.add_argument("--grouping", type=str, default="reference", choices=["reference", "tick"])
     ap.add_argument("--device", type=str, default="cuda:0")
-    ap.add_argument("--gpu-decode", action="store_true", help="decode the frames on the device (10 crops, frames at scale_size)")
+    ap.add_argument("--gpu-decode", action="store_true", help="decode the frames on the device (10 crops, frames at scale_size)"
+                    "; files rewritten with tools/transcode_frames.py (restart markers, same pixels) decode on one lane per interval instead of one per file")
     ap.add_argument("--gpu-scale", action="store_true", help="with --gpu-decode: frames of any size, GroupScale on the device")
     args = ap.parse_args(argv)
 

@@ -85,7 +85,8 @@ def main(argv=None):
     ap.add_argument("--pair-batch", type=int, default=16)
     ap.add_argument("--iterations", type=int, default=300)
     ap.add_argument("--jpeg-quality", type=int, default=95)
-    ap.add_argument("--gpu-decode", action="store_true", help="decode the input frames on the device (jpeg_decode.JpegDecoder)")
+    ap.add_argument("--gpu-decode", action="store_true", help="decode the input frames on the device (jpeg_decode.JpegDecoder)"
+                    "; files rewritten with tools/transcode_frames.py (restart markers, same pixels) decode on one lane per interval instead of one per file")
     ap.add_argument("--gpu-encode", action="store_true",
                     help="compress the flow images on the device (jpeg_encode.JpegEncoder): the same bytes, without PIL")
     ap.add_argument("--restart-blocks", type=int, default=0,

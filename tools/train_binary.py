@@ -45,7 +45,8 @@ def parse(argv=None):
     p.add_argument("--synthetic", type=int, default=0, metavar="N", help="N seeded batches instead of a data set")
     p.add_argument("--device", default="cuda:0")
     p.add_argument("--gpu-decode", action="store_true",
-                   help="upload the frames' JPEG files and decode them on the device (jpeg_decode.py) instead of PIL on the host")
+                   help="upload the frames' JPEG files and decode them on the device (jpeg_decode.py) instead of PIL on the host"
+                        "; files rewritten with tools/transcode_frames.py (restart markers, same pixels) decode on one lane per interval instead of one per file")
     return p.parse_args(argv)
 
 

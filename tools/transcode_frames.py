@@ -1,0 +1,136 @@
+#!/usr/bin/env python
+"""Rewrite a store of JPEG frames with restart markers, losslessly, on the device: ``jpegtran -restart`` for a whole data set.
+
+Every ``*.jpg`` / ``*.jpeg`` under SRC_ROOT is written to the same relative path under OUT_ROOT with the same quantised coefficients
+and quantisation tables -- the same pixels for every decoder -- and a restart marker every ``--restart-rows`` MCU rows (or every
+``--restart-blocks`` MCUs).  The device decoder (``--gpu-decode`` of the drivers, ``CompressedFrameDirReader``) takes one lane per
+restart interval instead of one per file, so pointing it at OUT_ROOT is all a consumer has to do.  Files the transcoder does not take
+(progressive, CMYK, damaged, ...: jpeg_transcode.py) are copied as they are; so is every file that is no JPEG.  The source's EXIF /
+ICC / comment segments are not carried over.
+
+    python tools/transcode_frames.py /data/frames /data/frames_rst --restart-rows 1 --verify
+
+Nothing under SRC_ROOT is written, renamed or deleted; OUT_ROOT may not be SRC_ROOT or lie inside it.  Every file is written under a
+temporary name and renamed, so an interrupted run leaves no half-written frame.  ``--verify`` decodes every source file and its
+output on the device and compares the pixels; a difference is an error exit.
+"""
+import argparse
+import os
+import shutil
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+_JPEG = (".jpg", ".jpeg")
+
+
+def list_files(src_root):
+    """(relative paths of the JPEG files, relative paths of everything else), sorted"""
+    jpegs, others = [], []
+    for d, _, files in sorted(os.walk(src_root)):
+        for name in sorted(files):
+            rel = os.path.relpath(os.path.join(d, name), src_root)
+            (jpegs if name.lower().endswith(_JPEG) else others).append(rel)
+    return jpegs, others
+
+
+def write_file(path, data):
+    """data (bytes) under a temporary name in the target's directory, then renamed over ``path``"""
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    tmp = "%s.tmp.%d" % (path, os.getpid())
+    try:
+        with open(tmp, "wb") as f:
+            f.write(data)
+        os.replace(tmp, path)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+
+
+def inside(path, root):
+    """Whether ``path`` is ``root`` or lies under it (symbolic links resolved)."""
+    path, root = os.path.realpath(path), os.path.realpath(root)
+    return path == root or path.startswith(root.rstrip(os.sep) + os.sep)
+
+
+def pixels_equal(decoder, sources, outputs, torch):
+    """Indices of the files whose output does not decode to the pixels of its source (both on the device)."""
+    a = decoder.decode(sources, "RGB")
+    b = decoder.decode(outputs, "RGB")
+    damaged = set(decoder.check())      # (an output whose scan does not decode cleanly is a difference, whatever PIL makes of it)
+    return [i for i, (x, y) in enumerate(zip(a, b)) if i in damaged or x.shape != y.shape or not torch.equal(x, y)]
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("src_root")
+    ap.add_argument("out_root")
+    ap.add_argument("--restart-rows", type=int, default=None, help="a restart marker every R rows of MCUs (default 1)")
+    ap.add_argument("--restart-blocks", type=int, default=None, help="a restart marker every K MCUs instead")
+    ap.add_argument("--batch", type=int, default=256, help="files per call of the transcoder")
+    ap.add_argument("--verify", action="store_true", help="decode source and output on the device and compare the pixels")
+    ap.add_argument("--quiet", action="store_true")
+    args = ap.parse_args(argv)
+    if args.restart_rows is not None and args.restart_blocks is not None:
+        ap.error("--restart-rows and --restart-blocks exclude each other")
+    if args.restart_rows is None and args.restart_blocks is None:
+        args.restart_rows = 1
+    if args.batch < 1:
+        ap.error("--batch is at least 1")
+    if not os.path.isdir(args.src_root):
+        ap.error("%s is no directory" % args.src_root)
+    if inside(args.out_root, args.src_root):
+        ap.error("OUT_ROOT (%s) is SRC_ROOT or lies inside it: the tool never writes under the source" % args.out_root)
+
+    import torch
+    from action_detection_amd import _lib
+    from action_detection_amd.jpeg_decode import JpegDecoder
+    from action_detection_amd.jpeg_transcode import JpegTranscoder
+    dev = torch.device("cpu") if _lib.emulator_active() else torch.device("cuda")
+    transcoder = JpegTranscoder(dev)
+    decoder = JpegDecoder(dev) if args.verify else None
+    jpegs, others = list_files(args.src_root)
+    for rel in others:
+        os.makedirs(os.path.dirname(os.path.join(args.out_root, rel)) or ".", exist_ok=True)
+        tmp = "%s.tmp.%d" % (os.path.join(args.out_root, rel), os.getpid())
+        shutil.copyfile(os.path.join(args.src_root, rel), tmp)
+        os.replace(tmp, os.path.join(args.out_root, rel))
+    done = bytes_in = bytes_out = 0
+    reasons, different = {}, []
+    for first in range(0, len(jpegs), args.batch):
+        names = jpegs[first:first + args.batch]
+        blobs = []
+        for rel in names:
+            with open(os.path.join(args.src_root, rel), "rb") as f:
+                blobs.append(f.read())
+        files = transcoder.transcode(blobs, restart_blocks=args.restart_blocks, restart_rows=args.restart_rows)
+        skipped = dict(transcoder.skipped)
+        if decoder is not None:
+            taken = [i for i in range(len(names)) if i not in skipped]
+            if taken:
+                different += [names[taken[j]] for j in pixels_equal(decoder, [blobs[i] for i in taken], [files[i] for i in taken], torch)]
+        for i, rel in enumerate(names):
+            write_file(os.path.join(args.out_root, rel), files[i])
+            bytes_in += len(blobs[i])
+            bytes_out += len(files[i])
+            if i in skipped:
+                reasons[skipped[i]] = reasons.get(skipped[i], 0) + 1
+                if not args.quiet:
+                    print("copied %s: %s" % (rel, skipped[i]))
+            else:
+                done += 1
+    n_skipped = sum(reasons.values())
+    print("%d files transcoded, %d copied unchanged%s, %d other files copied; %d bytes in, %d bytes out (%+.2f %%)%s" %
+          (done, n_skipped, "".join(" [%d: %s]" % (c, r) for r, c in sorted(reasons.items())), len(others), bytes_in, bytes_out,
+           100.0 * (bytes_out - bytes_in) / max(bytes_in, 1), "; verified: pixels equal" if args.verify and not different else ""))
+    if different:
+        print("VERIFY FAILED: %d files decode to other pixels than their source: %s" % (len(different), ", ".join(different[:10])),
+              file=sys.stderr)
+        return 2
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
