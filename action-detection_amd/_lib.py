@@ -19,7 +19,7 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(_HERE, "libssn_hip.so")
-SOURCES = ["conv_igemm.hip", "conv_x6.hip", "conv_x6_rect.hip", "conv_wgrad.hip", "conv_wgrad_x6.hip", "elementwise.hip", "bn_train.hip", "frames.hip", "detect.hip", "pool.hip", "stpp.hip", "heads_losses.hip", "conv_pl.hip", "planes_ops.hip", "planes_bn.hip", "wgrad_pl.hip", "tag.hip", "eval.hip", "actionness.hip", "train_step.hip", "flow.hip", "jpeg.hip", "jpeg_encode.hip", "jpeg_transcode.hip"]
+SOURCES = ["conv_igemm.hip", "conv_x6.hip", "conv_x6_rect.hip", "conv_wgrad.hip", "conv_wgrad_x6.hip", "elementwise.hip", "bn_train.hip", "frames.hip", "detect.hip", "pool.hip", "stpp.hip", "heads_losses.hip", "conv_pl.hip", "planes_ops.hip", "planes_bn.hip", "wgrad_pl.hip", "tag.hip", "eval.hip", "actionness.hip", "train_step.hip", "flow.hip", "jpeg.hip", "jpeg_encode.hip", "jpeg_transcode.hip", "video_cls.hip"]
 
 STPP_MAX_PARTS = 24
 
@@ -79,6 +79,13 @@ _SIGS = {
     "ssn_eval_count": "ppiipp",
     "ssn_eval_ap": "ppppippiippiippllpppplp",
     "ssn_eval_recall": "ppippiipipp",
+    "ssn_vcls_status": "ppiiipp",
+    "ssn_vcls_crop_reduce": "ppiiiip",
+    "ssn_vcls_window_max": "pppppiiiiipp",
+    "ssn_vcls_topk_mean": "pppiiipp",
+    "ssn_vcls_tpp": "ppiiiipp",
+    "ssn_vcls_finish": "pppiiilliipp",
+    "ssn_vcls_metrics": "ppppiiipppplp",
     "ssn_actionness_fc": "ppppiiiiiip",
     "ssn_actionness_group": "pppiiiip",
     "ssn_actionness_merge": "pppppiiiiip",
@@ -167,6 +174,7 @@ EXPORTS = sorted(list(_SIGS) + ["ssn_last_error", "ssn_abi_version", "ssn_conv_w
                                 "ssn_conv_debug_flags", "ssn_channel_sum_shares", "ssn_bn_train_workspace_floats",
                                 "ssn_conv_dgrad_layout", "ssn_conv_pl_tiles", "ssn_conv_pl_halo_taken", "ssn_conv_pl_debug_flags", "ssn_conv_pl_debug_trace", "ssn_conv_wgrad_pl_debug_trace", "ssn_conv_wgrad_pl_debug_flags", "ssn_conv_pl_tile_shape", "ssn_conv_wgrad_pl_tiles", "ssn_conv_wgrad_pl_workspace_bytes", "ssn_conv_wgrad_pl_group_workspace_bytes", "ssn_conv_wgrad_pl_group_table_bytes", "ssn_conv_wgrad_pl_group_tuning", "ssn_pl_channel_sum_workspace_bytes", "ssn_pl_bn_train_workspace_bytes", "ssn_conv_x6_pack_batch_entries", "ssn_conv_x6_pack_entry_bytes", "ssn_conv_x6_pack_batch_abort", "ssn_frames_resize_workspace_bytes", "ssn_frames_scale_workspace_bytes",
                                 "ssn_tag_workspace_bytes", "ssn_tag_lds_candidates", "ssn_eval_workspace_bytes", "ssn_eval_lds_gt",
+                                "ssn_vcls_lds_rows", "ssn_vcls_metrics_workspace_bytes",
                                 "ssn_sumsq_multi_workspace_floats", "ssn_train_step_launches"])
 
 
@@ -206,6 +214,10 @@ class SsnLibrary:
         self.cdll.ssn_eval_workspace_bytes.argtypes = [ctypes.c_long, ctypes.c_long, ctypes.c_int]
         self.cdll.ssn_eval_lds_gt.restype = ctypes.c_int
         self.cdll.ssn_eval_lds_gt.argtypes = []
+        self.cdll.ssn_vcls_lds_rows.restype = ctypes.c_int
+        self.cdll.ssn_vcls_lds_rows.argtypes = []
+        self.cdll.ssn_vcls_metrics_workspace_bytes.restype = ctypes.c_size_t
+        self.cdll.ssn_vcls_metrics_workspace_bytes.argtypes = [ctypes.c_int] * 2
         self.cdll.ssn_sumsq_multi_workspace_floats.restype = ctypes.c_long
         self.cdll.ssn_sumsq_multi_workspace_floats.argtypes = [ctypes.c_int, ctypes.c_void_p]
         self.cdll.ssn_train_step_launches.restype = ctypes.c_long

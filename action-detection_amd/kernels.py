@@ -979,6 +979,165 @@ def eval_recall(gt_span, gt_off, prop, prop_off, thresholds):
     return hits
 
 
+# ------------------------------------------------------------------------------------ video-level classification
+def vcls_lds_rows():
+    return int(_lib.get_lib().cdll.ssn_vcls_lds_rows())
+
+
+def _vcls_offsets(h_offsets, total, device, who, name="offsets"):
+    """A HOST int32 offset table [n + 1], checked here (ascending from 0 to `total`) -> its copy on `device`."""
+    if not torch.is_tensor(h_offsets) or h_offsets.is_cuda or h_offsets.dtype != torch.int32 or h_offsets.dim() != 1 \
+            or h_offsets.numel() < 2:
+        raise ValueError("%s: %s must be a host int32 tensor [n + 1], n >= 1" % (who, name))
+    if int(h_offsets[0]) != 0 or int(h_offsets[-1]) != int(total) or bool((h_offsets[1:] < h_offsets[:-1]).any()):
+        raise ValueError("%s: %s must ascend from 0 to %d" % (who, name, int(total)))
+    return h_offsets.contiguous().to(device)
+
+
+def _vcls_rows(x, rank, who, name="rows"):
+    if not torch.is_tensor(x) or x.dtype != torch.float32 or x.dim() != rank or min(x.shape[1:]) < 1:
+        raise ValueError("%s: %s must be float32 of rank %d with C >= 1, got %s %s" % (
+            who, name, rank, getattr(x, "dtype", type(x)), tuple(getattr(x, "shape", ()))))
+
+
+def vcls_status(x, h_offsets):
+    """ssn_vcls_status: x float32 [N, ...] ragged by the host offsets [V + 1] -> status [V] int32 on the device (1: a
+    non-finite value among the video's rows, 2: no rows)."""
+    lib = _check(x)
+    if not torch.is_tensor(x) or x.dtype != torch.float32 or x.dim() < 2 or min(x.shape[1:]) < 1:
+        raise ValueError("vcls_status: x must be float32 [N, ..., C >= 1]")
+    n = x.shape[0]
+    off = _vcls_offsets(h_offsets, n, x.device, "vcls_status")
+    v = off.numel() - 1
+    status = torch.empty(v, device=x.device, dtype=torch.int32)
+    lib.call("ssn_vcls_status", _p(x) if n else None, _p(off), v, n, x.shape[1:].numel(), _p(status), _stream(lib, x))
+    return status
+
+
+def vcls_crop_reduce(raw, use_max=False, out=None):
+    """ssn_vcls_crop_reduce: raw float32 [N, crops, C] -> [N, C], the crops' mean (added in order, one division) or maximum."""
+    lib = _check(raw, out)
+    _vcls_rows(raw, 3, "vcls_crop_reduce", "raw")
+    n, crops, c = raw.shape
+    if out is None:
+        out = torch.empty((n, c), device=raw.device, dtype=torch.float32)
+    if out.shape != (n, c) or out.dtype != torch.float32:
+        raise ValueError("vcls_crop_reduce: out must be float32 [%d, %d]" % (n, c))
+    lib.call("ssn_vcls_crop_reduce", _p(raw) if n else None, _p(out) if n else None, n, crops, c, int(bool(use_max)),
+             _stream(lib, raw))
+    return out
+
+
+def vcls_window_max(frm, h_offsets, h_win_off, spans, steps, out=None):
+    """ssn_vcls_window_max: frm float32 [N, C] ragged by the host offsets [V + 1]; spans / steps int32 [S] on the device;
+    h_win_off host int32 [V * S + 1] -> the window maxima [W, C], W = h_win_off[-1]."""
+    lib = _check(frm, spans, steps, out)
+    _vcls_rows(frm, 2, "vcls_window_max", "frm")
+    n, c = frm.shape
+    s = spans.numel()
+    if spans.dtype != torch.int32 or steps.dtype != torch.int32 or spans.dim() != 1 or steps.shape != spans.shape or s < 1:
+        raise ValueError("vcls_window_max: spans and steps must be int32 [S]")
+    off = _vcls_offsets(h_offsets, n, frm.device, "vcls_window_max")
+    v = off.numel() - 1
+    w = int(h_win_off[-1]) if torch.is_tensor(h_win_off) and h_win_off.numel() else -1
+    win = _vcls_offsets(h_win_off, w, frm.device, "vcls_window_max", "win_off")
+    if win.numel() != v * s + 1:
+        raise ValueError("vcls_window_max: win_off must hold V * S + 1 = %d entries" % (v * s + 1))
+    if out is None:
+        out = torch.empty((w, c), device=frm.device, dtype=torch.float32)
+    if out.shape != (w, c) or out.dtype != torch.float32:
+        raise ValueError("vcls_window_max: out must be float32 [%d, %d]" % (w, c))
+    lib.call("ssn_vcls_window_max", _p(frm) if n else None, _p(off), _p(win), _p(spans), _p(steps), v, s, n, c, w,
+             _p(out) if w else None, _stream(lib, frm))
+    return out
+
+
+def vcls_topk_mean(rows, h_seg_off, h_ks, out=None):
+    """ssn_vcls_topk_mean: rows float32 [N, C], host seg_off int32 [G + 1] and ks int32 [G] (each >= 1) -> [G, C]: per
+    class the mean of the min(k, n) largest rows of the segment."""
+    lib = _check(rows, out)
+    _vcls_rows(rows, 2, "vcls_topk_mean")
+    n, c = rows.shape
+    seg = _vcls_offsets(h_seg_off, n, rows.device, "vcls_topk_mean", "seg_off")
+    g = seg.numel() - 1
+    if not torch.is_tensor(h_ks) or h_ks.is_cuda or h_ks.dtype != torch.int32 or h_ks.shape != (g,):
+        raise ValueError("vcls_topk_mean: ks must be a host int32 tensor [%d]" % g)
+    if bool((h_ks < 1).any()):
+        raise ValueError("vcls_topk_mean: every k must be >= 1")
+    ks = h_ks.contiguous().to(rows.device)
+    if out is None:
+        out = torch.empty((g, c), device=rows.device, dtype=torch.float32)
+    if out.shape != (g, c) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("vcls_topk_mean: out must be contiguous float32 [%d, %d]" % (g, c))
+    lib.call("ssn_vcls_topk_mean", _p(rows) if n else None, _p(seg), _p(ks), g, n, c, _p(out), _stream(lib, rows))
+    return out
+
+
+def vcls_tpp(frm, h_offsets, num_class, out=None):
+    """ssn_vcls_tpp: frm float32 [N, stages * num_class] -> [V, num_class]."""
+    lib = _check(frm, out)
+    _vcls_rows(frm, 2, "vcls_tpp", "frm")
+    n, width = frm.shape
+    c = int(num_class)
+    if c < 1 or width % c:
+        raise ValueError("vcls_tpp: %d columns are not a multiple of num_class = %d" % (width, c))
+    off = _vcls_offsets(h_offsets, n, frm.device, "vcls_tpp")
+    v = off.numel() - 1
+    if out is None:
+        out = torch.empty((v, c), device=frm.device, dtype=torch.float32)
+    if out.shape != (v, c) or out.dtype != torch.float32:
+        raise ValueError("vcls_tpp: out must be float32 [%d, %d]" % (v, c))
+    lib.call("ssn_vcls_tpp", _p(frm) if n else None, _p(off), v, n, c, width // c, _p(out), _stream(lib, frm))
+    return out
+
+
+def vcls_finish(terms, video_axis, weights=None, status=None, divide=False, softmax=False, out=None):
+    """ssn_vcls_finish: terms float32 [V, S, C] (video_axis 0) or [S, V, C] (video_axis 1) -> [V, C]: the S terms of a
+    video added in order (terms 1 ... S - 1 times weights [S - 1] when given), divided by S when `divide`, NaN where
+    status [V] is not zero, then the optional softmax along C."""
+    lib = _check(terms, weights, status, out)
+    _vcls_rows(terms, 3, "vcls_finish", "terms")
+    if video_axis not in (0, 1):
+        raise ValueError("vcls_finish: video_axis must be 0 or 1")
+    v, s = (terms.shape[0], terms.shape[1]) if video_axis == 0 else (terms.shape[1], terms.shape[0])
+    c = terms.shape[2]
+    if v < 1 or s < 1:
+        raise ValueError("vcls_finish: no videos or no terms")
+    stride_v, stride_s = (s * c, c) if video_axis == 0 else (c, v * c)
+    if weights is not None and (weights.dtype != torch.float32 or weights.shape != (s - 1,)):
+        raise ValueError("vcls_finish: weights must be float32 [%d]" % (s - 1))
+    if status is not None and (status.dtype != torch.int32 or status.shape != (v,)):
+        raise ValueError("vcls_finish: status must be int32 [%d]" % v)
+    if out is None:
+        out = torch.empty((v, c), device=terms.device, dtype=torch.float32)
+    if out.shape != (v, c) or out.dtype != torch.float32:
+        raise ValueError("vcls_finish: out must be float32 [%d, %d]" % (v, c))
+    lib.call("ssn_vcls_finish", _p(terms), _p(weights) if weights is not None and s > 1 else None, _p(status), v, s, c,
+             stride_v, stride_s, int(bool(divide)), int(bool(softmax)), _p(out), _stream(lib, terms))
+    return out
+
+
+def vcls_metrics(scores, gt, label, top_ks):
+    """ssn_vcls_metrics: scores float32 [V, C], gt uint8 [V, C], label int32 [V] or None, top_ks int32 [K], all on the
+    device -> (counts int32 [K + 3 C], ap float64 [C], results float64 [K + 2]) on the device."""
+    lib = _check(scores, gt, label, top_ks)
+    _vcls_rows(scores, 2, "vcls_metrics", "scores")
+    v, c = scores.shape
+    if v < 1 or gt.shape != (v, c) or gt.dtype != torch.uint8 or top_ks.dtype != torch.int32 or top_ks.dim() != 1 \
+            or (label is not None and (label.shape != (v,) or label.dtype != torch.int32)):
+        raise ValueError("vcls_metrics: need V >= 1 videos, gt uint8 [V, C], label int32 [V], top_ks int32 [K]")
+    k = top_ks.numel()
+    dev = scores.device
+    counts = torch.empty(k + 3 * c, device=dev, dtype=torch.int32)
+    ap = torch.empty(c, device=dev, dtype=torch.float64)
+    results = torch.empty(k + 2, device=dev, dtype=torch.float64)
+    ws_bytes = int(lib.cdll.ssn_vcls_metrics_workspace_bytes(v, c))
+    ws = torch.empty((ws_bytes + 7) // 8, device=dev, dtype=torch.int64)
+    lib.call("ssn_vcls_metrics", _p(scores), _p(gt), _p(label), _p(top_ks) if k else None, v, c, k, _p(counts), _p(ap),
+             _p(results), _p(ws), ws_bytes, _stream(lib, scores))
+    return counts, ap, results
+
+
 def actionness_fc(feat, w, b, raw_true, tick0, num_crop):
     """ssn_actionness_fc: feat [num_crop * ticks, D] (crop-major backbone output of one call), w [C, D], b [C] or None ->
     raw_true[tick0 + t, c, :] = logits of feature row c * ticks + t; raw_true [T, num_crop, C] is the video's staging tensor."""

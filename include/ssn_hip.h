@@ -433,6 +433,37 @@ int ssn_eval_ap(const double* pred_seg, const double* pred_score, const int* pre
 int ssn_eval_recall(const double* gt_span, const int* gt_off, int G, const double* prop, const int* prop_off, int P, int V,
                     const double* thresholds, int T, int* hits, hipStream_t stream);
 
+/* Video-level classification (csrc/video_cls.hip): the aggregation functions of ops/video_funcs.py and the metrics of
+ * ops/metrics.py for a whole batch.  Rows of all videos one after the other, [N][C] fp32, ragged by offsets [V + 1] int32;
+ * every pointer but the sizes is device memory and no call's launches depend on V.
+ *   status       status [V] int32: 1 a non-finite value among the video's rows (x [N][width]), 2 no rows.
+ *   crop_reduce  raw [N][crops][C] -> frm [N][C]: crops added in order and divided once, or (use_max) their maximum.
+ *   window_max   window i of (video v, span s) covers ticks [i * steps[s], min(i * steps[s] + spans[s], T_v)); its per-class
+ *                maxima go to row win_off[v * S + s] + i of out [W][C]; win_off [V * S + 1]: prefix sums of ceil(T_v / steps[s]).
+ *   topk_mean    out [G][C]: per class the mean of the min(ks[g], n_g) largest of the rows seg_off[g] ... seg_off[g + 1], exact
+ *                in value with ties at the cut (k-th largest by a 32-pass threshold search on order-preserving keys); NaN
+ *                for a segment without rows.  ks[g] >= n_g: a plain sum.
+ *   tpp          frm [N][stages * C] -> out [V][C] = (1 / T) sum_t frm[t][k_t * C + c], k_t = int(t * (stages / T)) in fp64.
+ *   finish       out [V][C] = term 0 + sum_s w[s - 1] * term s (w NULL: 1), term s of video v at in + v * stride_v + s *
+ *                stride_s; `divide`: by S afterwards; status [V] (or NULL) non-zero: the row is NaN; `softmax`: along C.
+ *   metrics      scores [V][C], gt [V][C] uint8, label [V] int32 or NULL, top_ks [K] -> counts [K + 3 C] int32 (hits, class
+ *                hits / totals / predictions), ap [C] fp64 (tied scores form one threshold; NaN without a positive video),
+ *                results [K + 2] fp64: hit rates (stable ranking: of equal scores the higher class index ranks higher),
+ *                mean AP, mean class accuracy over the classes among labels or predictions (first argmax). */
+int ssn_vcls_lds_rows(void);
+size_t ssn_vcls_metrics_workspace_bytes(int V, int C);
+int ssn_vcls_status(const float* x, const int* offsets, int V, int N, int width, int* status, hipStream_t stream);
+int ssn_vcls_crop_reduce(const float* raw, float* frm, int N, int crops, int C, int use_max, hipStream_t stream);
+int ssn_vcls_window_max(const float* frm, const int* offsets, const int* win_off, const int* spans, const int* steps, int V,
+                        int S, int N, int C, int W, float* out, hipStream_t stream);
+int ssn_vcls_topk_mean(const float* rows, const int* seg_off, const int* ks, int G, int N, int C, float* out,
+                       hipStream_t stream);
+int ssn_vcls_tpp(const float* frm, const int* offsets, int V, int N, int C, int stages, float* out, hipStream_t stream);
+int ssn_vcls_finish(const float* in, const float* weights, const int* status, int V, int S, int C, long stride_v,
+                    long stride_s, int divide, int softmax, float* out, hipStream_t stream);
+int ssn_vcls_metrics(const float* scores, const unsigned char* gt, const int* label, const int* top_ks, int V, int C, int K,
+                     int* counts, double* ap, double* results, void* workspace, size_t ws_bytes, hipStream_t stream);
+
 /* The scoring tail of the actionness stage and the merge in front of TAG (csrc/actionness.hip).
  * fc: test_fc on the backbone output of one call (binary_test.py:89, binary_model.py:237-240; a cuBLAS GEMM in the reference).
  *   feat [num_crop * ticks][D] fp32 crop-major, w [C][D], b [C] or NULL -> raw_true [T][num_crop][C], the video's staging

@@ -44,6 +44,9 @@ def parse(argv=None):
     p.add_argument("--frame-root", default="")
     p.add_argument("--synthetic", type=int, default=0, metavar="N", help="N seeded batches instead of a data set")
     p.add_argument("--device", default="cuda:0")
+    p.add_argument("--num-class", type=int, default=2,
+                   help="outputs of the classifier (2: actionness; K: the video-level classifier tools/classify_videos.py scores with; "
+                        "the targets are whatever the data source yields)")
     p.add_argument("--gpu-decode", action="store_true",
                    help="upload the frames' JPEG files and decode them on the device (jpeg_decode.py) instead of PIL on the host"
                         "; files rewritten with tools/transcode_frames.py (restart markers, same pixels) decode on one lane per interval instead of one per file")
@@ -64,7 +67,7 @@ def main(argv=None):
 
     pkg.build()
     new_length = 1 if args.modality == "RGB" else 5
-    model = BinaryClassifier(2, args.num_body_segments, args.modality, new_length=new_length, base_model=args.arch, dropout=0.8,
+    model = BinaryClassifier(args.num_class, args.num_body_segments, args.modality, new_length=new_length, base_model=args.arch, dropout=0.8,
                              bn_mode=args.bn_mode)      # (binary_train.py:25 fixes the dropout)
     if args.init_weights:
         model.base_model.load_state_dict(torch.load(args.init_weights, map_location="cpu", weights_only=False)["state_dict"])
