@@ -99,6 +99,8 @@ _SIGS = {
     "ssn_jpeg_entropy": "plpipipiplpp",
     "ssn_jpeg_idct": "plpiipiplp",
     "ssn_jpeg_pixels": "plpiliplp",
+    "ssn_jpeg_index": "plpipipp",
+    "ssn_jpeg_index_status": "ppip",
     "ssn_jpeg_enc_layout": "pp",
     "ssn_jpeg_enc_blocks": "plpiipplp",
     "ssn_jpeg_enc_count": "plpiipppp",

@@ -6,6 +6,7 @@
 //   ssn_jpeg_entropy   Huffman decode, one LANE per restart interval (or per scan of a file without restart markers)
 //   ssn_jpeg_idct      dequantise + inverse DCT, one thread per 8 x 8 block, into padded component planes
 //   ssn_jpeg_pixels    upsample + colour conversion + crop, one thread per output pixel
+//   ssn_jpeg_index     optional, in front of the entropy stage: the restart intervals of every file, one workgroup per file
 //
 // The host (jpeg_decode.py) walks the markers and writes three device tables:
 //   desc   int32 [images][JPEG_DESC_INTS]   geometry and the image's offsets into the coefficient, plane and output buffers
@@ -352,6 +353,168 @@ __global__ __launch_bounds__(256) void jpeg_pixels_kernel(const unsigned char* p
     }
 }
 
+// ---- restart-interval index: the marker search of jpeg_decode._parse_scan on the device --------------------------------------
+// The host uploads every file from the first byte of its entropy-coded data to the file's end (each file's first byte at a
+// multiple of 16) and, in the spare columns of its desc row, where: its byte range in `bits`, its first unit row and the units its
+// header promises.  The unit rows arrive with everything the bytes do not decide (image, MCU range, table set, workgroup pair,
+// padding rows); the kernel fills U_BEGIN / U_END.  One workgroup per file walks it in order, JPEG_IX_CHUNK bytes at a time:
+//   a marker is a position i with b[i] == FF and b[i + 1] neither 00 nor FF (the last byte of a file has no b[i + 1]);
+//   the scan ends at the first marker that is not RST0..7 (or at the file's end), restart markers behind it are ignored;
+//   the k-th restart marker at p ends unit k at p and begins unit k + 1 at p + 2; units past the last found one get (end, end).
+// More restart markers than the promised units hold, or another SOS / a DNL among the segments behind the scan, set
+// JPEG_ST_INDEX in the file's word of `refused`.  Nothing in the desc row is trusted: the byte range is clamped to `bits`, the row
+// range to the table, and a row is written only if it names this file; whatever had to be clamped refuses the file as well.
+enum { D_IX_BEGIN = 15, D_IX_END, D_IX_ROW0, D_IX_NUNITS };
+enum { JPEG_ST_INDEX = 16 };
+constexpr int JPEG_IX_THREADS = 256;
+constexpr int JPEG_IX_WAVES = JPEG_IX_THREADS / 64;
+constexpr int JPEG_IX_CHUNK = JPEG_IX_THREADS * 16;
+constexpr int JPEG_IX_NONE = 0x7FFFFFFF;
+
+typedef unsigned int jpeg_u32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ void jpeg_index_put(int* units, int n_units, int file, int row0, int nunits, int k, int col, int value) {
+    if (k < 0 || k >= nunits) return;
+    const long row = (long)row0 + k;
+    if (row < 0 || row >= n_units) return;
+    int* u = units + row * JPEG_UNIT_INTS;
+    if (u[U_IMAGE] == file) u[col] = value;
+}
+
+__global__ __launch_bounds__(JPEG_IX_THREADS) void jpeg_index_kernel(const unsigned char* bits, long bits_bytes, const int* desc, int* units,
+                                                                     int n_units, int* refused) {
+    __shared__ int s_min[JPEG_IX_WAVES];
+    __shared__ int s_cnt[JPEG_IX_WAVES];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int file = blockIdx.x;
+    const int* d = desc + (long)file * JPEG_DESC_INTS;
+    int nunits = d[D_IX_NUNITS], row0 = d[D_IX_ROW0];
+    if (nunits == 0) {                                   // a file the kernels do not take: nothing to index
+        if (tid == 0) refused[file] = 0;
+        return;
+    }
+    int flags = 0;
+    long fb = d[D_IX_BEGIN], fe = d[D_IX_END];
+    if (fb < 0 || fe < fb || fe > bits_bytes || (fb & 15)) {
+        flags = JPEG_ST_INDEX;
+        fb = fe = 0;                                     // (nothing of such a file is read)
+    }
+    const long room = (long)n_units - row0;              // rows from the file's first to the table's end
+    if (nunits < 0 || row0 < 0 || room <= 0 || nunits > room) {
+        flags = JPEG_ST_INDEX;
+        nunits = (nunits < 0 || row0 < 0 || room <= 0) ? 0 : (int)room;
+    }
+    if (nunits > 0 && units[(long)row0 * JPEG_UNIT_INTS + U_IMAGE] != file) flags = JPEG_ST_INDEX;      // another file's rows
+
+    int base = 0;                                        // restart markers in front of the chunk
+    int end = (int)fe;                                   // the scan's end, once found
+    for (long chunk = fb; chunk < fe; chunk += JPEG_IX_CHUNK) {
+        const long p = chunk + (long)tid * 16;
+        // ---- this lane's 16 bytes and the one behind them; bytes at or past the file's end read as 00
+        unsigned w[4] = {0u, 0u, 0u, 0u};
+        if (p + 16 <= fe) {
+            const jpeg_u32x4 v = *reinterpret_cast<const jpeg_u32x4*>(bits + p);
+            w[0] = v[0];
+            w[1] = v[1];
+            w[2] = v[2];
+            w[3] = v[3];
+        } else {
+            for (int j = 0; j < 16; ++j)
+                if (p + j < fe) w[j >> 2] |= (unsigned)bits[p + j] << (8 * (j & 3));
+        }
+        unsigned next = (unsigned)__shfl_down((int)(w[0] & 0xFFu), 1, 64);
+        if (lane == 63) next = 0u;
+        const bool last_ff = (w[3] >> 24) == 0xFFu;
+        if (lane == 63 && last_ff && p + 16 < fe) next = bits[p + 16];      // (a wave's, and a chunk's, edge)
+        unsigned rst = 0u, other = 0u;
+        unsigned any_ff = 0u;                                              // (the zero-byte test on the complement)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) any_ff |= (~w[i] - 0x01010101u) & w[i] & 0x80808080u;
+        if (any_ff) {
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const unsigned cur = (w[j >> 2] >> (8 * (j & 3))) & 0xFFu;
+                const unsigned nx = j == 15 ? next : (w[(j + 1) >> 2] >> (8 * ((j + 1) & 3))) & 0xFFu;
+                const bool marker = cur == 0xFFu && nx != 0u && nx != 0xFFu;
+                const bool restart = (nx & 0xF8u) == 0xD0u;
+                rst |= (marker && restart ? 1u : 0u) << j;
+                other |= (marker && !restart ? 1u : 0u) << j;
+            }
+        }
+        // ---- the first marker of the chunk that is not a restart marker: wave minimum, then across the waves
+        int first = other ? (int)p + __builtin_ctz(other) : JPEG_IX_NONE;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const int o = __shfl_xor(first, off, 64);
+            first = o < first ? o : first;
+        }
+        if (lane == 0) s_min[wave] = first;
+        __syncthreads();
+        first = s_min[0];
+#pragma unroll
+        for (int i = 1; i < JPEG_IX_WAVES; ++i) first = s_min[i] < first ? s_min[i] : first;
+        // ---- restart markers in front of it: exclusive prefix over the lanes, then over the waves
+        if (first != JPEG_IX_NONE) {
+            const long keep = (long)first - p;
+            rst = keep <= 0 ? 0u : (keep < 16 ? rst & ((1u << keep) - 1u) : rst);
+        }
+        const int mine = __builtin_popcount(rst);
+        int incl = mine;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int o = __shfl(incl, lane >= off ? lane - off : lane, 64);
+            if (lane >= off) incl += o;
+        }
+        if (lane == 63) s_cnt[wave] = incl;
+        __syncthreads();
+        int k = base + incl - mine, total = 0;
+#pragma unroll
+        for (int i = 0; i < JPEG_IX_WAVES; ++i) {
+            if (i < wave) k += s_cnt[i];
+            total += s_cnt[i];
+        }
+        while (rst) {
+            const int at = (int)p + __builtin_ctz(rst);
+            rst &= rst - 1u;
+            jpeg_index_put(units, n_units, file, row0, nunits, k, U_END, at);
+            jpeg_index_put(units, n_units, file, row0, nunits, k + 1, U_BEGIN, at + 2);
+            ++k;
+        }
+        base += total;
+        if (first != JPEG_IX_NONE) {
+            end = first;
+            break;                                       // (uniform: every lane holds the same `first`)
+        }
+    }
+    if (base > nunits - 1) flags = JPEG_ST_INDEX;        // more restart markers than the interval allows (or than no DRI allows: none)
+    // ---- unit 0 begins at the file's begin, the last found unit ends at the scan's end, the promised rest is empty there
+    const int found = base + 1 < nunits ? base + 1 : nunits;
+    if (tid == 0) jpeg_index_put(units, n_units, file, row0, nunits, 0, U_BEGIN, (int)fb);
+    if (tid == 0) jpeg_index_put(units, n_units, file, row0, nunits, base, U_END, end);
+    for (int k = found + tid; k < nunits; k += JPEG_IX_THREADS) {
+        jpeg_index_put(units, n_units, file, row0, nunits, k, U_BEGIN, end);
+        jpeg_index_put(units, n_units, file, row0, nunits, k, U_END, end);
+    }
+    // ---- what follows the scan, segment by segment on one lane: anything but another scan or a DNL (normally just FF D9)
+    if (tid == 0) {
+        long q = end;
+        while (q + 4 <= fe && bits[q] == 0xFFu && bits[q + 1] != 0xD9u) {
+            const unsigned m = bits[q + 1];
+            if (m == 0xDAu || m == 0xDCu) {
+                flags = JPEG_ST_INDEX;
+                break;
+            }
+            q += m == 0xFFu ? 1 : 2 + (long)(((unsigned)bits[q + 2] << 8) | bits[q + 3]);
+        }
+        refused[file] = flags;
+    }
+}
+
+__global__ __launch_bounds__(256) void jpeg_index_status_kernel(const int* refused, int* status, int n_images) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n_images && refused[i]) status[i] |= refused[i];
+}
+
 }  // namespace
 
 // the sizes the host builds its tables with
@@ -405,5 +568,27 @@ extern "C" int ssn_jpeg_pixels(const unsigned char* planes, long plane_bytes, co
     hipLaunchKernelGGL(jpeg_pixels_kernel, dim3((unsigned)((max_pixels + 255) / 256), (unsigned)n_images), dim3(256), 0, stream, planes,
                        plane_bytes, desc, out_c, out, out_bytes);
     SSN_CHECK_LAUNCH("jpeg_pixels");
+    return SSN_OK;
+}
+
+// The restart-interval index of a batch: fills U_BEGIN / U_END of the unit rows the desc rows name (columns 15 .. 18: first byte,
+// end byte, first unit row, units) and writes refused int32 [n_images]: 16 for a file the index does not take, else 0.
+extern "C" int ssn_jpeg_index(const unsigned char* bits, long bits_bytes, const int* desc, int n_images, int* units, int n_units,
+                              int* refused, hipStream_t stream) {
+    SSN_CHECK_ARG(n_images >= 1 && n_units >= 64 && n_units % 64 == 0, "jpeg_index: bad counts (units come in rows of 64)");
+    SSN_CHECK_ARG(bits_bytes >= 0 && bits_bytes < (1L << 31), "jpeg_index: bad buffer size");
+    SSN_CHECK_ARG((bits || bits_bytes == 0) && desc && units && refused, "jpeg_index: null pointer");
+    SSN_CHECK_ARG(((uintptr_t)bits & 15) == 0, "jpeg_index: bits must be 16-byte aligned");
+    hipLaunchKernelGGL(jpeg_index_kernel, dim3((unsigned)n_images), dim3(JPEG_IX_THREADS), 0, stream, bits, bits_bytes, desc, units, n_units,
+                       refused);
+    SSN_CHECK_LAUNCH("jpeg_index");
+    return SSN_OK;
+}
+
+// status[i] |= refused[i]: after ssn_jpeg_entropy, which zeroes status
+extern "C" int ssn_jpeg_index_status(const int* refused, int* status, int n_images, hipStream_t stream) {
+    SSN_CHECK_ARG(n_images >= 1 && refused && status, "jpeg_index_status: bad arguments");
+    hipLaunchKernelGGL(jpeg_index_status_kernel, dim3((unsigned)((n_images + 255) / 256)), dim3(256), 0, stream, refused, status, n_images);
+    SSN_CHECK_LAUNCH("jpeg_index_status");
     return SSN_OK;
 }

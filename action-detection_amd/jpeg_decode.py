@@ -6,6 +6,8 @@ restart interval.  ``JpegDecoder.decode`` uploads the scans of a batch of files 
 enqueues three launches (csrc/jpeg.hip: entropy decode, inverse DCT, upsample + colour conversion + crop) on the caller's stream,
 without a host read.  Files the kernels do not take (progressive, CMYK, 4:1:1, ...) are decoded by PIL on the host and uploaded
 instead; ``JpegDecoder.fallbacks`` counts them.  The pixels are PIL's, bit for bit, for the libjpeg PIL links.
+With ``JpegDecoder(index="device")`` the host reads the headers only (``parse_jpeg_header``) and a fourth launch in front of the
+others (``ssn_jpeg_index``) finds the restart intervals in the uploaded bytes.
 """
 import io
 import re
@@ -102,6 +104,41 @@ def parse_jpeg(data):
                 _header_cache.clear()
             _header_cache[key] = h
     return _parse_scan(copy.copy(h), data, n, begin) if h.supported else h
+
+
+_last_header = [None]      # (header bytes, JpegHeader) of the last supported file parse_jpeg_header saw
+
+
+def parse_jpeg_header(data):
+    """The header part of ``parse_jpeg`` without the scan walk -> ``JpegHeader`` with ``scan = (begin, len(data))`` and no units:
+    what ``JpegDecoder(index="device")`` needs of the host (the kernel finds the restart intervals and the scan's end).  The last
+    header is tried first: a file that starts with the very bytes of that header, up to and including its SOS segment, has that
+    header, and costs one comparison instead of a segment walk."""
+    import copy
+    data = bytes(data)
+    n = len(data)
+    last = _last_header[0]
+    if last is not None and data.startswith(last[0]):
+        h = copy.copy(last[1])
+        h.scan, h.units = (len(last[0]), n), []
+        return h
+    begin = _scan_begin(data, n) if n >= 4 and data[0] == 0xFF and data[1] == 0xD8 else -1
+    key = data[:begin] if begin > 0 else None
+    h = _header_cache.get(key) if key is not None else None
+    if h is None:
+        h = _parse_header(data, n)
+        if key is not None and h.supported:
+            if len(_header_cache) > 256:
+                _header_cache.clear()
+            _header_cache[key] = h
+    if not h.supported:
+        return h
+    if key is None:
+        return copy.copy(h)._no("no scan")
+    _last_header[0] = (key, h)
+    h = copy.copy(h)
+    h.scan, h.units = (begin, n), []
+    return h
 
 
 def _parse_header(data, n):
@@ -326,9 +363,20 @@ class JpegDecoder(object):
     read back.  ``status`` (int32 [files], on the device) is non-zero for a file whose scan was damaged: 1 it ran out of data,
     2 an undefined Huffman code, 4 a coefficient past the end of a block, 8 an unusable table row.  ``check()`` is the one optional
     host read: it looks at ``status`` and replaces the damaged files of the last batch by PIL's decoding.  ``fallbacks`` counts the
-    files PIL decoded on the host: the ones ``parse_jpeg`` does not support, and after ``check()`` the damaged ones."""
+    files PIL decoded on the host: the ones ``parse_jpeg`` does not support, and after ``check()`` the damaged ones.
 
-    def __init__(self, device="cuda:0"):
+    ``index`` says who finds the restart intervals.  "host" (the default): ``parse_jpeg`` walks every scan.  "device": the host
+    reads the headers only (``parse_jpeg_header``), copies every file once, from its first scan byte to its end, into the pinned
+    upload buffer, and ``ssn_jpeg_index`` searches the markers and fills the unit table in front of the entropy launch; the host
+    does a constant amount of work per file and none per restart interval or per byte.  The one difference in behaviour: what the
+    host walk refuses by looking at the scan (restart markers that do not fit the header's interval, a second scan, a DNL marker)
+    the device finds after the call has returned, so such a file is not decoded by PIL inside ``decode`` -- it gets bit 16 in
+    ``status``, unspecified pixels, and is decoded by PIL and counted in ``fallbacks`` by ``check()``, like a damaged file."""
+
+    def __init__(self, device="cuda:0", index="host"):
+        if index not in ("host", "device"):
+            raise ValueError("JpegDecoder: index is 'host' or 'device'")
+        self.index = index
         self.device = torch.device(device)
         self.cuda = self.device.type == "cuda"
         self.fallbacks = 0
@@ -414,6 +462,130 @@ class JpegDecoder(object):
                      max_blocks=max_blocks, max_pixels=max_pixels)
         return staging, offs, sizes
 
+    def _plan_device(self, blobs, headers):
+        """``_plan`` for ``index="device"``: per file one desc row (columns 15 .. 18: where ``ssn_jpeg_index`` finds the file's bytes
+        and its unit rows) and ONE copy of its bytes, from the first scan byte to the file's end, into the upload buffer; the unit
+        rows -- everything but begin / end, which the kernel fills -- with numpy, whatever the number of restart intervals.
+        -> (upload buffer, section offsets, sizes, the desc rows)."""
+        n = len(blobs)
+        desc = np.zeros((n, self.desc_ints), np.int32)
+        sets, set_rows, quant, quant_rows = {}, [], {}, []
+        image, fset, fcount, fri, fmcus, spans = [], [], [], [], [], []
+        bits_off = coef_off = plane_off = 0
+        out_off = self._out_off
+        max_blocks = max_pixels = 0
+        for i, (blob, h) in enumerate(zip(blobs, headers)):
+            if h is None:
+                continue
+            mx, my = h.mcus
+            nc = len(h.components)
+            luma, chroma = mx * h.hs * my * h.vs, mx * my
+            nblocks = luma + (2 * chroma if nc == 3 else 0)
+            qi = []
+            for c, key in zip(h.components, h.quant_keys):
+                if key not in quant:
+                    quant[key] = len(quant_rows)
+                    quant_rows.append(h.qtables[c[3]])
+                qi.append(quant[key])
+            qi += [0] * (3 - nc)
+            key = h.table_key
+            if key not in sets:
+                sets[key] = len(set_rows)
+                row = np.zeros((4, self.table_words), np.int32)
+                for j, tab in enumerate(key):
+                    if tab is not None:
+                        row[j] = _table_words(tab[0], tab[1], self.table_words)
+                set_rows.append(row)
+            ri, size = h.restart_interval, len(blob) - h.scan[0]
+            count = -(-chroma // ri) if ri else 1
+            desc[i, :19] = (h.width, h.height, nc, h.hs, h.vs, mx, my, coef_off, nblocks, plane_off, out_off[i], qi[0], qi[1], qi[2],
+                            h.table_select, bits_off, bits_off + size, 0, count)
+            image.append(i)
+            fset.append(sets[key])
+            fcount.append(count)
+            fri.append(ri)
+            fmcus.append(chroma)
+            spans.append((bits_off, h.scan[0], size))
+            bits_off += _align(size)
+            coef_off += nblocks
+            plane_off += nblocks * 64
+            max_blocks, max_pixels = max(max_blocks, nblocks), max(max_pixels, h.width * h.height)
+        if coef_off >= (1 << 25) or bits_off >= (1 << 31) or out_off[-1] >= (1 << 31):
+            raise ValueError("JpegDecoder: the batch is too large for one call (2^25 blocks, 2 GiB of scans or of pixels)")
+        # the files' rows, as _plan lays its sorted units out: by table set, in workgroups of 64 rows that span at most lds_sets sets.
+        # A file's units share its set, so a break the sets force falls in front of a file: one step per FILE decides the rows.
+        image, fset, fcount = np.array(image, np.int64), np.array(fset, np.int64), np.array(fcount, np.int64)
+        order = np.argsort(fset, kind="stable")
+        row0 = [0] * len(order)
+        pos = first = first_set = 0
+        for j, s, k in zip(order.tolist(), fset[order].tolist(), fcount[order].tolist()):
+            if pos > first and s - first_set >= self.lds_sets:
+                pos = first = first + 64
+            if pos == first:
+                first_set = s
+            row0[j] = pos
+            pos += k
+            if pos - first >= 64:
+                first, first_set = first + (pos - first) // 64 * 64, s
+        row0 = np.array(row0, np.int64)
+        desc[image, 17] = row0
+        nrows = _align(pos, 64)
+        if nrows >= (1 << 31) // (4 * self.unit_ints):
+            raise ValueError("JpegDecoder: too many restart intervals for one call")
+        counts = fcount[order]
+        rep = np.repeat(np.arange(len(order)), counts)                          # the (sorted) file of every unit
+        k = np.arange(int(counts.sum())) - np.repeat(np.cumsum(counts) - counts, counts)      # its number inside the file
+        at = row0[order][rep] + k
+        ri, mcus = np.array(fri, np.int64)[order][rep], np.array(fmcus, np.int64)[order][rep]
+        urows = np.zeros((nrows, self.unit_ints), np.int32)
+        urows[:, 0] = -1
+        urows[at, 0] = image[order][rep]
+        urows[at, 3] = k * ri
+        urows[at, 4] = np.where(ri > 0, np.minimum(ri, mcus - k * ri), mcus)
+        urows[at, 5] = fset[order][rep]
+        live = urows[:, 0].reshape(-1, 64) >= 0
+        wg = urows[:, 5].reshape(-1, 64)
+        lo = np.where(live, wg, 1 << 30).min(axis=1)
+        urows[::64, 6] = lo
+        urows[::64, 7] = np.where(live, wg, -1).max(axis=1) - lo + 1
+        sections = [None, desc.view(np.uint8).reshape(-1), urows.view(np.uint8).reshape(-1),
+                    np.stack(set_rows).view(np.uint8).reshape(-1), np.stack(quant_rows).view(np.uint8).reshape(-1)]
+        offs, total = [0], _align(max(bits_off, 1))
+        for sec in sections[1:]:
+            offs.append(total)
+            total += _align(max(sec.size, 1))
+        staging = self._staging(total)
+        flat = staging.numpy()
+        for blob, (o, b0, size) in zip((blobs[i] for i in image.tolist()), spans):
+            flat[o:o + size] = np.frombuffer(blob, np.uint8, size, b0)
+        for o, sec in zip(offs[1:], sections[1:]):
+            flat[o:o + sec.size] = sec
+        sizes = dict(bits=bits_off, units=nrows, sets=len(set_rows), quant=len(quant_rows), blocks=coef_off, planes=plane_off,
+                     max_blocks=max_blocks, max_pixels=max_pixels)
+        return staging, offs, sizes, desc
+
+    def _staging(self, nbytes):
+        """The buffer the next batch is assembled in: a slice of one of the two pinned buffers (host memory on a non-HIP device)."""
+        if not self.cuda:
+            return torch.empty(nbytes, dtype=torch.uint8)
+        turn = self._turn
+        if self._event[turn] is not None:
+            self._event[turn].synchronize()      # the copy that last read this pinned buffer is done
+        if self._pinned[turn] is None or self._pinned[turn].numel() < nbytes:
+            self._pinned[turn] = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, pin_memory=True)
+        return self._pinned[turn][:nbytes]
+
+    def _send(self, staging):
+        """Start the copy of what ``_staging`` handed out."""
+        if not self.cuda:
+            return staging
+        turn = self._turn
+        self._turn ^= 1
+        dev = staging.to(self.device, non_blocking=True)
+        self._event[turn] = torch.cuda.Event()
+        self._event[turn].record(torch.cuda.current_stream(self.device))
+        return dev
+
     def _upload(self, staging):
         t = torch.from_numpy(staging)
         if not self.cuda:
@@ -445,6 +617,16 @@ class JpegDecoder(object):
     def _alloc(self, shape, dtype):
         return torch.empty(shape, dtype=dtype, device=self.device)
 
+    def _entropy(self, bits, desc, units, tables, coef):
+        """The entropy launch; with ``index="device"`` between the index launch, which completes the unit rows, and the launch
+        that ORs its verdicts into ``status`` (the entropy launch zeroes ``status``)."""
+        if self.index == "device":
+            refused = self._alloc((desc.shape[0],), torch.int32)
+            self._timed("index", K.jpeg_index, bits, desc, units, refused)
+        self._timed("entropy", K.jpeg_entropy, bits, desc, units, tables, coef, self.status)
+        if self.index == "device":
+            self._timed("verdicts", K.jpeg_index_status, refused, self.status)
+
     # -- decode ------------------------------------------------------------------------------------------------------------
     def decode(self, blobs, mode="RGB", stack=False):
         if mode not in ("RGB", "L"):
@@ -454,8 +636,9 @@ class JpegDecoder(object):
             raise ValueError("JpegDecoder: no files")
         out_c = 3 if mode == "RGB" else 1
         headers, host, shapes = [], {}, []
+        parse = parse_jpeg_header if self.index == "device" else parse_jpeg
         for i, blob in enumerate(blobs):
-            h = parse_jpeg(blob)
+            h = parse(blob)
             if h.supported:
                 headers.append(h)
                 shapes.append((h.height, h.width))
@@ -474,9 +657,14 @@ class JpegDecoder(object):
         self.status = torch.zeros(n, dtype=torch.int32, device=self.device)
         self.uploaded_bytes = 0
         if len(host) < n:
-            staging, offs, sz = self._plan(blobs, headers, out_c)
-            self.uploaded_bytes = staging.size
-            dev = self._timed("upload", self._upload, staging)
+            if self.index == "device":
+                staging, offs, sz, _ = self._plan_device(blobs, headers)
+                self.uploaded_bytes = staging.numel()
+                dev = self._timed("upload", self._send, staging)
+            else:
+                staging, offs, sz = self._plan(blobs, headers, out_c)
+                self.uploaded_bytes = staging.size
+                dev = self._timed("upload", self._upload, staging)
             bits = dev[offs[0]:offs[0] + sz["bits"]]
             desc = dev[offs[1]:offs[1] + n * self.desc_ints * 4].view(torch.int32).view(n, self.desc_ints)
             units = dev[offs[2]:offs[2] + sz["units"] * self.unit_ints * 4].view(torch.int32).view(-1, self.unit_ints)
@@ -484,10 +672,11 @@ class JpegDecoder(object):
             quant = dev[offs[4]:offs[4] + sz["quant"] * 128].view(torch.int16).view(-1, 64)
             coef = self._alloc((sz["blocks"], 64), torch.int16)
             planes = self._alloc((sz["planes"],), torch.uint8)
-            self._timed("entropy", K.jpeg_entropy, bits, desc, units, tables, coef, self.status)
+            self._entropy(bits, desc, units, tables, coef)
             self._timed("idct", K.jpeg_idct, coef, desc, sz["max_blocks"], quant, planes)
             self._timed("pixels", K.jpeg_pixels, planes, desc, sz["max_pixels"], out_c, out)
             self._stages = (desc, coef, planes, quant, sz)      # (kept for the stage-level tests)
+            self._unit_rows = units
         views = [out[self._out_off[i]:self._out_off[i + 1]].view(shapes[i][0], shapes[i][1], out_c) for i in range(n)]
         for i, a in host.items():
             self.uploaded_bytes += a.size
@@ -504,7 +693,8 @@ class JpegDecoder(object):
         blobs = [bytes(b) for b in blobs]
         if not blobs:
             raise ValueError("JpegDecoder: no files")
-        parsed = [parse_jpeg(blob) for blob in blobs]
+        parse = parse_jpeg_header if self.index == "device" else parse_jpeg
+        parsed = [parse(blob) for blob in blobs]
         headers = [h if h.supported else None for h in parsed]
         n = len(blobs)
         self._out_off = [0] * (n + 1)      # (no pixels: the rows' output offsets are not used)
@@ -513,16 +703,21 @@ class JpegDecoder(object):
         self._last = None
         if all(h is None for h in headers):
             return CoefficientBatch(parsed, None, None, self.status, 0)
-        staging, offs, sz = self._plan(blobs, headers, 1)
-        self.uploaded_bytes = staging.size
-        dev = self._timed("upload", self._upload, staging)
+        if self.index == "device":
+            staging, offs, sz, rows = self._plan_device(blobs, headers)
+            self.uploaded_bytes = staging.numel()
+            dev = self._timed("upload", self._send, staging)
+        else:
+            staging, offs, sz = self._plan(blobs, headers, 1)
+            self.uploaded_bytes = staging.size
+            dev = self._timed("upload", self._upload, staging)
+            rows = np.frombuffer(staging, np.int32, n * self.desc_ints, offs[1]).reshape(n, self.desc_ints)
         bits = dev[offs[0]:offs[0] + sz["bits"]]
         desc = dev[offs[1]:offs[1] + n * self.desc_ints * 4].view(torch.int32).view(n, self.desc_ints)
         units = dev[offs[2]:offs[2] + sz["units"] * self.unit_ints * 4].view(torch.int32).view(-1, self.unit_ints)
         tables = dev[offs[3]:offs[3] + sz["sets"] * 16 * self.table_words].view(torch.int32).view(-1, 4, self.table_words)
         coef = self._alloc((sz["blocks"], 64), torch.int16)
-        self._timed("entropy", K.jpeg_entropy, bits, desc, units, tables, coef, self.status)
-        rows = np.frombuffer(staging, np.int32, n * self.desc_ints, offs[1]).reshape(n, self.desc_ints)
+        self._entropy(bits, desc, units, tables, coef)
         return CoefficientBatch(parsed, coef, desc, self.status, sz["max_blocks"], rows)
 
     def check(self):
@@ -547,8 +742,8 @@ class CompressedBatchPrefetcher(TrainingBatchPrefetcher):
     uint8 frames to the same transform; about 14 times fewer bytes cross PCIe than with decoded frames.  On a non-HIP device it
     degrades to the synchronous loop, as the parent class does."""
 
-    def __init__(self, source, transform, depth=2, group_size=None):
-        self.decoder = JpegDecoder(transform.mean.device)
+    def __init__(self, source, transform, depth=2, group_size=None, index="host"):
+        self.decoder = JpegDecoder(transform.mean.device, index=index)
         self.mode = "L" if transform.is_flow else "RGB"
         super().__init__(source, transform, depth=depth, group_size=group_size)
 

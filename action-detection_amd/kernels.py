@@ -1646,6 +1646,33 @@ def jpeg_pixels(planes, desc, max_pixels, out_c, out):
              _stream(lib, out))
 
 
+def jpeg_index(bits, desc, units, refused):
+    """ssn_jpeg_index: bits uint8 [bytes], 16-byte aligned, every file from its first scan byte to its end; desc int32 [images,
+    desc_ints] with columns 15 .. 18 (first byte, end byte, first unit row, units) filled; units int32 [64 k, unit_ints] (begin / end
+    of the files' rows are written); refused int32 [images] (written: 16 or 0)."""
+    lib = _check(bits, desc, units, refused)
+    n = _jpeg_desc(desc)
+    unit_ints = jpeg_layout()[1]
+    if bits.dtype != torch.uint8 or bits.dim() != 1 or bits.numel() >= 1 << 31:
+        raise ValueError("jpeg_index: bits must be uint8 [bytes], less than 2 GiB")
+    if bits.numel() and bits.data_ptr() % 16:
+        raise ValueError("jpeg_index: bits must be 16-byte aligned")
+    if units.dtype != torch.int32 or units.dim() != 2 or units.shape[1] != unit_ints or units.shape[0] < 64 or units.shape[0] % 64:
+        raise ValueError("jpeg_index: units must be int32 [64 k, %d]" % unit_ints)
+    if refused.dtype != torch.int32 or refused.shape != (n,):
+        raise ValueError("jpeg_index: refused must be int32 [images]")
+    lib.call("ssn_jpeg_index", _p(bits) if bits.numel() else None, bits.numel(), _p(desc), n, _p(units), units.shape[0], _p(refused),
+             _stream(lib, units))
+
+
+def jpeg_index_status(refused, status):
+    """ssn_jpeg_index_status: status |= refused, both int32 [images]; after jpeg_entropy, which zeroes status."""
+    lib = _check(refused, status)
+    if refused.dtype != torch.int32 or status.dtype != torch.int32 or refused.dim() != 1 or refused.shape != status.shape or not refused.numel():
+        raise ValueError("jpeg_index_status: refused and status must be int32 [images]")
+    lib.call("ssn_jpeg_index_status", _p(refused), _p(status), refused.numel(), _stream(lib, status))
+
+
 # ------------------------------------------------------------------------------------ baseline JPEG encoding (csrc/jpeg_encode.hip)
 def jpeg_enc_layout():
     """(desc_ints, block_bits): ints of a desc row jpeg_encode.py builds, and the most bits the codes of one block take."""

@@ -790,6 +790,21 @@ int ssn_jpeg_idct(const short* coef, long total_blocks, const int* desc, int n_i
 int ssn_jpeg_pixels(const unsigned char* planes, long plane_bytes, const int* desc, int n_images, long max_pixels, int out_c,
                     unsigned char* out, long out_bytes, hipStream_t stream);
 
+/* The restart-interval index of a batch on the device (csrc/jpeg.hip): replaces the marker search of jpeg_decode._parse_scan and the
+ * per-unit loop of JpegDecoder._plan.  bits holds every file from the first byte of its entropy-coded data to the file's end, each
+ * file's first byte at a multiple of 16; columns 15 .. 18 of a file's desc row say where: first byte, end byte, first unit row,
+ * units its header promises (ceil(MCUs / restart interval), 1 without a DRI; 0: the file is not indexed).  The unit rows arrive with
+ * everything the bytes do not decide (image, MCU range, table set, workgroup pair, padding rows).
+ *  index         one workgroup per file, 16 bytes per lane: a marker is FF followed by neither 00 nor FF, the scan ends at the first
+ *                marker that is not RST0..7 (or at the file's end), the k-th restart marker at p ends unit k at p and begins unit
+ *                k + 1 at p + 2, units the data does not contain get (end, end).  Writes begin / end of the file's rows (only rows
+ *                inside the table that name the file) and refused int32 [images]: 16 for more restart markers than the promised
+ *                units allow, another SOS or a DNL behind the scan, or a desc row whose ranges had to be clamped; else 0.
+ *  index_status  status[i] |= refused[i], after ssn_jpeg_entropy (which zeroes status). */
+int ssn_jpeg_index(const unsigned char* bits, long bits_bytes, const int* desc, int n_images, int* units, int n_units, int* refused,
+                   hipStream_t stream);
+int ssn_jpeg_index_status(const int* refused, int* status, int n_images, hipStream_t stream);
+
 /* Baseline JPEG encoding of a batch of images (csrc/jpeg_encode.hip): the bytes PIL's Image.save(f, "JPEG", quality=, subsampling=,
  * restart_marker_blocks=) writes, byte for byte, for the libjpeg PIL links.  The host (jpeg_encode.py) describes
  * the batch in desc int32 [images][desc_ints] and prepares the quantisation tables (uint16 [2][64], natural order), the Huffman code

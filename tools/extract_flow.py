@@ -87,6 +87,7 @@ def main(argv=None):
     ap.add_argument("--jpeg-quality", type=int, default=95)
     ap.add_argument("--gpu-decode", action="store_true", help="decode the input frames on the device (jpeg_decode.JpegDecoder)"
                     "; files rewritten with tools/transcode_frames.py (restart markers, same pixels) decode on one lane per interval instead of one per file")
+    ap.add_argument("--device-index", action="store_true", help="with --gpu-decode: find the restart intervals on the device too (JpegDecoder(index=\"device\")): no host work per interval or per byte")
     ap.add_argument("--gpu-encode", action="store_true",
                     help="compress the flow images on the device (jpeg_encode.JpegEncoder): the same bytes, without PIL")
     ap.add_argument("--restart-blocks", type=int, default=0,
@@ -102,7 +103,7 @@ def main(argv=None):
     decoder = None
     if args.gpu_decode:
         from action_detection_amd.jpeg_decode import JpegDecoder
-        decoder = JpegDecoder(dev)
+        decoder = JpegDecoder(dev, index="device" if args.device_index else "host")
     if args.restart_blocks and not args.gpu_encode:
         ap.error("--restart-blocks needs --gpu-encode")
     encoder = None

@@ -60,6 +60,8 @@ def parse(argv=None):
     p.add_argument("--gpu-decode", action="store_true",
                    help="upload the frames' JPEG files and decode them on the device (jpeg_decode.py) instead of PIL on the host"
                         "; files rewritten with tools/transcode_frames.py (restart markers, same pixels) decode on one lane per interval instead of one per file")
+    p.add_argument("--device-index", action="store_true",
+                   help="with --gpu-decode: find the restart intervals on the device too (JpegDecoder(index=\"device\")): no host work per interval or per byte")
     return p.parse_args(argv)
 
 
@@ -117,7 +119,9 @@ def main(argv=None):
             raise SystemExit("--train-list, --val-list and --frame-root are needed without --synthetic")
         if args.gpu_decode:
             from action_detection_amd.jpeg_decode import CompressedBatchPrefetcher
-            Prefetcher, batches = CompressedBatchPrefetcher, D.compressed_ssn_batches
+            import functools
+            Prefetcher = functools.partial(CompressedBatchPrefetcher, index="device" if args.device_index else "host")
+            batches = D.compressed_ssn_batches
             reader = D.CompressedFrameDirReader(args.frame_root, args.modality, args.flow_prefix)
         else:
             reader = D.FrameDirReader(args.frame_root, args.modality, args.flow_prefix)

@@ -90,7 +90,7 @@ def main(argv=None):
     from action_detection_amd.jpeg_transcode import JpegTranscoder
     dev = torch.device("cpu") if _lib.emulator_active() else torch.device("cuda")
     transcoder = JpegTranscoder(dev)
-    decoder = JpegDecoder(dev) if args.verify else None
+    decoder = JpegDecoder(dev, index="device") if args.verify else None      # (both decodes of --verify index on the device)
     jpegs, others = list_files(args.src_root)
     for rel in others:
         os.makedirs(os.path.dirname(os.path.join(args.out_root, rel)) or ".", exist_ok=True)
