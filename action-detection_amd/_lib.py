@@ -19,7 +19,7 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(_HERE, "libssn_hip.so")
-SOURCES = ["conv_igemm.hip", "conv_x6.hip", "conv_x6_rect.hip", "conv_wgrad.hip", "conv_wgrad_x6.hip", "elementwise.hip", "bn_train.hip", "frames.hip", "detect.hip", "pool.hip", "stpp.hip", "heads_losses.hip", "conv_pl.hip", "planes_ops.hip", "planes_bn.hip", "wgrad_pl.hip", "tag.hip", "eval.hip", "actionness.hip", "train_step.hip", "flow.hip", "jpeg.hip", "jpeg_encode.hip", "jpeg_transcode.hip", "video_cls.hip"]
+SOURCES = ["conv_igemm.hip", "conv_x6.hip", "conv_x6_rect.hip", "conv_wgrad.hip", "conv_wgrad_x6.hip", "elementwise.hip", "bn_train.hip", "frames.hip", "detect.hip", "pool.hip", "stpp.hip", "heads_losses.hip", "conv_pl.hip", "planes_ops.hip", "planes_bn.hip", "wgrad_pl.hip", "tag.hip", "eval.hip", "actionness.hip", "train_step.hip", "flow.hip", "jpeg.hip", "jpeg_encode.hip", "jpeg_transcode.hip", "video_cls.hip", "proposal_list.hip"]
 
 STPP_MAX_PARTS = 24
 
@@ -79,6 +79,9 @@ _SIGS = {
     "ssn_eval_count": "ppiipp",
     "ssn_eval_ap": "ppppippiippiippllpppplp",
     "ssn_eval_recall": "ppippiipipp",
+    "ssn_sw_count": "pippipp",
+    "ssn_sw_fill": "pippiipp",
+    "ssn_proposal_list_rows": "ppippippipppp",
     "ssn_vcls_status": "ppiiipp",
     "ssn_vcls_crop_reduce": "ppiiiip",
     "ssn_vcls_window_max": "pppppiiiiipp",

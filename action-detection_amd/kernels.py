@@ -979,6 +979,71 @@ def eval_recall(gt_span, gt_off, prop, prop_off, thresholds):
     return hits
 
 
+# ------------------------------------------------------------------------------------ proposal lists
+def _sw_levels(spans, steps, who):
+    """Host int32 arrays of the per-level span / step tables (kept alive by the caller for the duration of the call)."""
+    spans, steps = [int(x) for x in spans], [int(x) for x in steps]
+    if len(spans) < 1 or len(spans) > 31 or len(spans) != len(steps):
+        raise ValueError("%s: 1 ... 31 levels with one span and one step each, got %d / %d" % (who, len(spans), len(steps)))
+    if min(spans) < 1 or min(steps) < 1 or max(spans) >= 2 ** 31 or max(steps) >= 2 ** 31:
+        raise ValueError("%s: spans and steps must be int32 >= 1, got %r / %r" % (who, spans, steps))
+    n = len(spans)
+    return (ctypes.c_int * n)(*spans), (ctypes.c_int * n)(*steps), n
+
+
+def sw_count(durations, spans, steps):
+    """ssn_sw_count: durations [V] fp64 (device), spans / steps: host lists of the per-level t_span and step ->
+    counts [V, L] int32 (device)."""
+    lib = _check(durations)
+    if durations.dim() != 1 or durations.dtype != torch.float64 or durations.numel() < 1:
+        raise ValueError("sw_count: durations must be float64 [V >= 1], got %s %s" % (durations.dtype, tuple(durations.shape)))
+    h_spans, h_steps, n = _sw_levels(spans, steps, "sw_count")
+    v = durations.numel()
+    counts = torch.zeros((v, n), device=durations.device, dtype=torch.int32)
+    lib.call("ssn_sw_count", _p(durations), v, ctypes.addressof(h_spans), ctypes.addressof(h_steps), n, _p(counts),
+             _stream(lib, durations))
+    return counts
+
+
+def sw_fill(offsets, spans, steps, total):
+    """ssn_sw_fill: offsets [V * L + 1] int32 (device, exclusive prefix sums of the counts, last entry `total`) ->
+    windows [total, 2] fp64 (device)."""
+    lib = _check(offsets)
+    h_spans, h_steps, n = _sw_levels(spans, steps, "sw_fill")
+    total = int(total)
+    if offsets.dim() != 1 or offsets.dtype != torch.int32 or offsets.numel() < n + 1 or (offsets.numel() - 1) % n:
+        raise ValueError("sw_fill: offsets must be int32 [V * L + 1], got %s %s for %d levels"
+                         % (offsets.dtype, tuple(offsets.shape), n))
+    if total < 0 or total >= 2 ** 30:
+        raise ValueError("sw_fill: %d windows in one batch, split it" % total)
+    windows = torch.zeros((total, 2), device=offsets.device, dtype=torch.float64)
+    lib.call("ssn_sw_fill", _p(offsets), (offsets.numel() - 1) // n, ctypes.addressof(h_spans), ctypes.addressof(h_steps), n,
+             total, _p(windows) if total else None, _stream(lib, offsets))
+    return windows
+
+
+def proposal_list_rows(gt_span, gt_off, prop, prop_off, frame_cnt, durations):
+    """ssn_proposal_list_rows: gt_span [G, 2] fp64, gt_off [V + 1] int32, prop [P, 2] fp64, prop_off [V + 1] int32, frame_cnt
+    [V] int32, durations [V] fp64 -> (gt_frames [G, 2] int32, frames [P, 2] int32, status [V] int32)."""
+    lib = _check(gt_span, gt_off, prop, prop_off, frame_cnt, durations)
+    g, p, v = gt_span.shape[0], prop.shape[0], durations.numel()
+    if gt_span.shape != (g, 2) or gt_span.dtype != torch.float64 or prop.shape != (p, 2) or prop.dtype != torch.float64:
+        raise ValueError("proposal_list_rows: spans must be float64 [G, 2] / [P, 2]")
+    if v < 1 or durations.shape != (v,) or durations.dtype != torch.float64 or frame_cnt.shape != (v,) \
+            or frame_cnt.dtype != torch.int32:
+        raise ValueError("proposal_list_rows: durations must be float64 [V >= 1] and frame_cnt int32 [V]")
+    if gt_off.shape != (v + 1,) or gt_off.dtype != torch.int32 or prop_off.shape != (v + 1,) or prop_off.dtype != torch.int32:
+        raise ValueError("proposal_list_rows: gt_off / prop_off must be int32 [V + 1]")
+    dev = durations.device
+    gt_frames = torch.zeros((g, 2), device=dev, dtype=torch.int32)
+    frames = torch.zeros((p, 2), device=dev, dtype=torch.int32)
+    status = torch.zeros(v, device=dev, dtype=torch.int32)
+    lib.call("ssn_proposal_list_rows", _p(gt_span) if g else None, _p(gt_off), g, _p(prop) if p else None, _p(prop_off), p,
+             _p(frame_cnt), _p(durations), v, _p(gt_frames) if g else None, _p(frames) if p else None, _p(status),
+             _stream(lib, durations))
+    return gt_frames, frames, status
+
+
 # ------------------------------------------------------------------------------------ video-level classification
 def vcls_lds_rows():
     return int(_lib.get_lib().cdll.ssn_vcls_lds_rows())

@@ -15,6 +15,9 @@ Two flavours share one layout::
 ``load_proposal_file`` returns the reference's tuples ``(vid, n_frame, gt_boxes, pr_boxes)`` with the box fields
 still as strings; ``process_proposal_list`` converts normalised positions to frame indices.
 """
+import fnmatch
+import glob
+import os
 
 
 def _records(lines):
@@ -58,6 +61,32 @@ def format_window_list_record(path, frame_cnt, duration, gt, named_proposals):
            for p in named_proposals]
     return "{}\n{}\n{}\n{}\n{}{}\n{}\n".format(path, frame_cnt, 1, len(gts), "\n".join(gts) + ("\n" if gts else ""),
                                                len(prs), "\n".join(prs))
+
+
+def format_window_list_rows(path, frame_cnt, gt_labels, gt_frames, labels, iou, overlap_self, frames):
+    """The text of ``format_window_list_record`` from the arrays of ``proposal_lists.ProposalListBuilder.build`` (one
+    video: ``result.rows(i)``), whose positions are frame numbers already: gt_labels [n] (label + 1, as written),
+    gt_frames [n, 2], labels / iou / overlap_self [K], frames [K, 2]."""
+    # (%-formatting of whole columns: the same digits as the reference's '{:.04f}'.format, cheaper than a format call per field)
+    gts = list(map("%d %d %d".__mod__, zip(gt_labels.tolist(), gt_frames[:, 0].tolist(), gt_frames[:, 1].tolist())))
+    prs = list(map("%d %.4f %.4f %d %d".__mod__, zip(labels.tolist(), iou.tolist(), overlap_self.tolist(),
+                                                     frames[:, 0].tolist(), frames[:, 1].tolist())))
+    return "{}\n{}\n{}\n{}\n{}{}\n{}\n".format(path, frame_cnt, 1, len(gts), "\n".join(gts) + ("\n" if gts else ""),
+                                               len(prs), "\n".join(prs))
+
+
+def parse_directory(path, key_func=lambda x: x[-11:], rgb_prefix='img_', flow_x_prefix='flow_x_', flow_y_prefix='flow_y_'):
+    """``frame_dict[key_func(folder)] = (folder, RGB frames, flow frames)`` for every folder under ``path``, counted by file
+    name prefix (/root/reference/ops/io.py:64-93); a folder with different numbers of x and y flow images is an error.
+    Folders are taken in alphabetical order (of two with one key the later wins)."""
+    frame_dict = {}
+    for folder in sorted(glob.glob(os.path.join(path, '*'))):
+        names = os.listdir(folder)
+        rgb, x_cnt, y_cnt = (len(fnmatch.filter(names, prefix + '*')) for prefix in (rgb_prefix, flow_x_prefix, flow_y_prefix))
+        if x_cnt != y_cnt:
+            raise ValueError('x and y direction have different number of flow images. video: ' + folder)
+        frame_dict[key_func(folder)] = (folder, rgb, x_cnt)
+    return frame_dict
 
 
 def write_proposal_file(filename, records):

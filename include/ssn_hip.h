@@ -433,6 +433,31 @@ int ssn_eval_ap(const double* pred_seg, const double* pred_score, const int* pre
 int ssn_eval_recall(const double* gt_span, const int* gt_off, int G, const double* prop, const int* prop_off, int P, int V,
                     const double* thresholds, int T, int* hits, hipStream_t stream);
 
+/* The proposal-list stage for a batch of videos (csrc/proposal_list.hip); naming and recall run on the two entries above,
+ * on the device tensors these write.  fp64 / int32 only, every fp64 result one IEEE operation.
+ *   sw_count / sw_fill   gen_exponential_sw_proposal (ops/sequence_funcs.py:37-54; called at gen_sliding_window_proposals.py:46):
+ *                        level l has windows (k * step_l, k * step_l + span_l), k < ceil(duration / step_l) (the entries of
+ *                        np.arange(0, duration, step_l)), kept while min(duration, start + span_l) - start >= 1 -- a prefix
+ *                        in k.  durations [V] fp64 (device); h_spans / h_steps [L] int32 on the HOST (span_l = 2^l, step_l =
+ *                        int(ceil(span_l * time_step * (1 - overlap))), both >= 1, L <= 31; validated before any launch).
+ *                        Two phases with ONE host read between them: counts [V][L] int32, from which the caller forms
+ *                        offsets [V * L + 1] int32 (exclusive prefix sums, total W < 2^30); then windows [W][2] fp64 in the
+ *                        reference's order (per video: level ascending, start ascending).
+ *   proposal_list_rows   the frame-number columns of dump_window_list (ops/io.py:109-127; called at
+ *                        gen_sliding_window_proposals.py:62 and gen_bottom_up_proposals.py:185): per video real_fps =
+ *                        double(frame_cnt) / duration, every span (s, e) of gt_span [G][2] (ragged by gt_off [V + 1]) and of
+ *                        prop [P][2] (ragged by prop_off [V + 1]) becomes (int(s * real_fps), int(e * real_fps)), truncated
+ *                        toward zero: gt_frames [G][2], frames [P][2] int32.  A product that is not finite or does not fit
+ *                        int32 is written as 0 and sets bit 0 (ground truth) or bit 1 (proposal) of its video's word in
+ *                        status [V] int32; other videos are unaffected.  All pointers device memory. */
+int ssn_sw_count(const double* durations, int V, const int* h_spans, const int* h_steps, int L, int* counts,
+                 hipStream_t stream);
+int ssn_sw_fill(const int* offsets, int V, const int* h_spans, const int* h_steps, int L, int W, double* windows,
+                hipStream_t stream);
+int ssn_proposal_list_rows(const double* gt_span, const int* gt_off, int G, const double* prop, const int* prop_off, int P,
+                           const int* frame_cnt, const double* durations, int V, int* gt_frames, int* frames, int* status,
+                           hipStream_t stream);
+
 /* Video-level classification (csrc/video_cls.hip): the aggregation functions of ops/video_funcs.py and the metrics of
  * ops/metrics.py for a whole batch.  Rows of all videos one after the other, [N][C] fp32, ragged by offsets [V + 1] int32;
  * every pointer but the sizes is device memory and no call's launches depend on V.
