@@ -19,7 +19,7 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(_HERE, "libssn_hip.so")
-SOURCES = ["conv_igemm.hip", "conv_x6.hip", "conv_x6_rect.hip", "conv_wgrad.hip", "conv_wgrad_x6.hip", "elementwise.hip", "bn_train.hip", "frames.hip", "detect.hip", "pool.hip", "stpp.hip", "heads_losses.hip", "conv_pl.hip", "planes_ops.hip", "planes_bn.hip", "wgrad_pl.hip", "tag.hip", "eval.hip", "actionness.hip", "train_step.hip", "flow.hip", "jpeg.hip", "jpeg_encode.hip", "jpeg_transcode.hip", "video_cls.hip", "proposal_list.hip"]
+SOURCES = ["conv_igemm.hip", "conv_x6.hip", "conv_x6_rect.hip", "conv_wgrad.hip", "conv_wgrad_x6.hip", "elementwise.hip", "bn_train.hip", "frames.hip", "detect.hip", "detect_batch.hip", "pool.hip", "stpp.hip", "heads_losses.hip", "conv_pl.hip", "planes_ops.hip", "planes_bn.hip", "wgrad_pl.hip", "tag.hip", "eval.hip", "actionness.hip", "train_step.hip", "flow.hip", "jpeg.hip", "jpeg_encode.hip", "jpeg_transcode.hip", "video_cls.hip", "proposal_list.hip"]
 
 STPP_MAX_PARTS = 24
 
@@ -73,6 +73,8 @@ _SIGS = {
     "ssn_stpp_reorg": "piippppiiiiipppp",
     "ssn_crop_mean": "ppiiip",
     "ssn_detections": "ppppppppuiiiiidip",
+    "ssn_detections_batch": "pppppppliiiidpppppup",
+    "ssn_detections_batch_fill": "ppppppiillippppp",
     "ssn_tag_count": "pppiipidppppp",
     "ssn_tag_generate": "ppppiipipippllddppppppppup",
     "ssn_tag_name_proposals": "pppippiidpppp",
@@ -175,7 +177,7 @@ _CT = {"p": ctypes.c_void_p, "i": ctypes.c_int, "l": ctypes.c_long, "f": ctypes.
 
 EXPORTS = sorted(list(_SIGS) + ["ssn_last_error", "ssn_abi_version", "ssn_conv_wgrad_workspace_bytes",
                                 "ssn_conv_pick_tile", "ssn_conv_packed_floats", "ssn_conv_x6_packed_floats", "ssn_conv_x6_packed_floats_rect", "ssn_conv_x6_packed_floats_dgrad_rect", "ssn_conv_wgrad_x6_rect_workspace_bytes", "ssn_conv_x6_dgrad_s2_packed_floats", "ssn_conv_x6_debug_flags", "ssn_conv_x6_debug_trace",
-                                "ssn_conv_wgrad_x6_workspace_bytes", "ssn_detections_workspace_bytes",
+                                "ssn_conv_wgrad_x6_workspace_bytes", "ssn_detections_workspace_bytes", "ssn_detections_batch_workspace_bytes",
                                 "ssn_conv_debug_flags", "ssn_channel_sum_shares", "ssn_bn_train_workspace_floats",
                                 "ssn_conv_dgrad_layout", "ssn_conv_pl_tiles", "ssn_conv_pl_halo_taken", "ssn_conv_pl_debug_flags", "ssn_conv_pl_debug_trace", "ssn_conv_wgrad_pl_debug_trace", "ssn_conv_wgrad_pl_debug_flags", "ssn_conv_pl_tile_shape", "ssn_conv_wgrad_pl_tiles", "ssn_conv_wgrad_pl_workspace_bytes", "ssn_conv_wgrad_pl_group_workspace_bytes", "ssn_conv_wgrad_pl_group_table_bytes", "ssn_conv_wgrad_pl_group_tuning", "ssn_pl_channel_sum_workspace_bytes", "ssn_pl_bn_train_workspace_bytes", "ssn_conv_x6_pack_batch_entries", "ssn_conv_x6_pack_entry_bytes", "ssn_conv_x6_pack_batch_abort", "ssn_frames_resize_workspace_bytes", "ssn_frames_scale_workspace_bytes",
                                 "ssn_tag_workspace_bytes", "ssn_tag_lds_candidates", "ssn_eval_workspace_bytes", "ssn_eval_lds_gt",
@@ -211,6 +213,8 @@ class SsnLibrary:
         self.cdll.ssn_conv_wgrad_x6_workspace_bytes.argtypes = [ctypes.c_int] * 7
         self.cdll.ssn_detections_workspace_bytes.restype = ctypes.c_size_t
         self.cdll.ssn_detections_workspace_bytes.argtypes = [ctypes.c_int] * 2
+        self.cdll.ssn_detections_batch_workspace_bytes.restype = ctypes.c_size_t
+        self.cdll.ssn_detections_batch_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_long]
         self.cdll.ssn_tag_workspace_bytes.restype = ctypes.c_size_t
         self.cdll.ssn_tag_workspace_bytes.argtypes = [ctypes.c_long] * 2
         self.cdll.ssn_tag_lds_candidates.restype = ctypes.c_int
@@ -287,7 +291,7 @@ def build(force=False, verbose=False):
     a multi-GPU launch all call this)."""
     import fcntl
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
-    deps = srcs + [os.path.join(CSRC, h) for h in ("ssn_common.h", "conv_epilogue.h", "conv_x6_kernel.h", "planes.h", "conv_pl_epilogue.inc")]
+    deps = srcs + [os.path.join(CSRC, h) for h in ("ssn_common.h", "conv_epilogue.h", "conv_x6_kernel.h", "planes.h", "conv_pl_epilogue.inc", "detect_common.h")]
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
     stamp_path = LIB_PATH + ".stamp"
     want = _source_stamp(deps, flags)

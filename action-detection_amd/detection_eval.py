@@ -132,12 +132,13 @@ class DetectionEvaluator(object):
         self._videos = {}            # video id -> index, in the order of add_video
         self._host = []              # (video index, class, rows [n, 3])
         self._dev = []               # (video index, dets [C, n_max, 5], counts [C]) on the device
+        self._batches = []           # (index of the batch's first video, detection_post.BatchedDetections)
 
     def add_video(self, video_id, detections):
         """detections: what ``DetectionPostProcessor.process_video`` returns first, ``{class: rows [n, >= 3]}`` (start, end,
         score; further columns ignored, as ravel_detections' ``x[:3]``), or the pair ``(dets [C, n_max, 5], counts [C])``
-        of ``process_video_device``, which stays on the device.  Flat row order (the tie rule's "input order"): videos
-        in the order they were added, those given on the host first."""
+        of ``process_video_device``, which stays on the device.  Flat row order (the tie rule's "input order"): the rows
+        given on the host, then the per-video device entries, then the batches of ``add_batch``, each in the order added."""
         if video_id in self._videos:
             raise ValueError("video %r was added before" % (video_id,))
         index = len(self._videos)
@@ -160,6 +161,21 @@ class DetectionEvaluator(object):
                 raise ValueError("device detections must be (dets [C, n_max, >= 3], counts [C]) tensors, C <= num_class")
             self._dev.append((index, dets, counts))
         self._videos[video_id] = index
+
+    def add_batch(self, batched):
+        """batched: what ``DetectionPostProcessor.process_videos`` returns.  Its flat rows are appended as they are (no
+        padding, nothing to compact); its videos count as added in the batch's order."""
+        if batched.num_class > self.num_class:
+            raise ValueError("a batch of %d classes for an evaluator of %d" % (batched.num_class, self.num_class))
+        seen = set()
+        for video_id in batched.video_ids:
+            if video_id in self._videos or video_id in seen:
+                raise ValueError("video %r was added before" % (video_id,))
+            seen.add(video_id)
+        base = len(self._videos)
+        for video_id in batched.video_ids:
+            self._videos[video_id] = len(self._videos)
+        self._batches.append((base, batched))
 
     def _flat_rows(self, dev):
         """-> seg [N, 2], score [N] float64, cls, vid [N] int32 on `dev`.  A constant number of transfers and torch calls."""
@@ -189,6 +205,9 @@ class DetectionEvaluator(object):
             parts.append((padded[:, :2].contiguous(), padded[:, 2].contiguous(),
                           _put(np.concatenate(cls), dev).index_select(0, keep),
                           _put(np.concatenate(vid), dev).index_select(0, keep)))
+        for base, b in self._batches:
+            rows = b.rows.to(dev)
+            parts.append((rows[:, :2].contiguous(), rows[:, 2].contiguous(), b.cls.to(dev), b.vid.to(dev) + base))
         if not parts:
             return (torch.zeros((0, 2), dtype=torch.float64, device=dev), torch.zeros(0, dtype=torch.float64, device=dev),
                     torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(0, dtype=torch.int32, device=dev))

@@ -838,6 +838,75 @@ def detections(act, comp, reg, rel_prop, top_k, include_bg, nms_thresh, regress)
     return combined, dets, counts
 
 
+def detections_batch_check_sizes(total_p, v, c):
+    """The size limit of the batched path, on shapes alone (before anything is concatenated or allocated)."""
+    if int(total_p) * int(c) >= 2 ** 31 or int(v) * int(c) >= 2 ** 31:
+        raise ValueError("detections_batch: %d proposals of %d videos x %d classes do not fit int32 indices, split the batch"
+                         % (total_p, v, c))
+
+
+def detections_batch(act, comp, rel_prop, h_p_off, d_p_off, report, top_k, include_bg, nms_thresh):
+    """All videos of a batch, stages scores / select / nms / offsets (ssn_detections_batch): act [total_p, C + 1], comp
+    [total_p, C] fp32, rel_prop [total_p, 2] fp64, h_p_off / d_p_off [V + 1] int32 (host / device copy), report [V, C] uint8
+    or None -> (combined [total_p, C] fp32, kept [total_p * C] int32, row_off [V * C + 1] int32), all on the device."""
+    lib = _check(act, comp, rel_prop, d_p_off, report)
+    total_p, c = comp.shape
+    if h_p_off.is_cuda or h_p_off.dtype != torch.int32 or d_p_off.dtype != torch.int32 or h_p_off.dim() != 1 \
+            or h_p_off.shape != d_p_off.shape or h_p_off.numel() < 2 or not h_p_off.is_contiguous():
+        raise ValueError("detections_batch: offsets must be int32 [V + 1], once on the host and once on the device")
+    v = h_p_off.numel() - 1
+    if c < 1 or act.shape != (total_p, c + 1) or rel_prop.shape != (total_p, 2) or rel_prop.dtype != torch.float64 \
+            or act.dtype != torch.float32 or comp.dtype != torch.float32 or int(h_p_off[-1]) != total_p:
+        raise ValueError("detections_batch: act must be float32 [P, C + 1], comp float32 [P, C], rel_prop float64 [P, 2], "
+                         "P the last offset")
+    if report is not None and (report.shape != (v, c) or report.dtype != torch.uint8):
+        raise ValueError("detections_batch: report must be uint8 [V, C]")
+    detections_batch_check_sizes(total_p, v, c)
+    dev = comp.device
+    # workspace entries of the videos whose candidates do not fit in LDS (host arithmetic on the offsets alone)
+    sizes = (h_p_off[1:] - h_p_off[:-1]).to(torch.int64)
+    pow2 = torch.ones_like(sizes)
+    while bool((pow2 < sizes).any()):
+        pow2 = torch.where(pow2 < sizes, pow2 * 2, pow2)
+    big_off = torch.zeros(v + 1, dtype=torch.int64)
+    big_off[1:] = torch.cumsum(torch.where(sizes > 2048, pow2 * c, torch.zeros_like(sizes)), 0)
+    big_entries = int(big_off[-1])
+    combined = torch.empty((total_p, c), device=dev, dtype=torch.float32)
+    kept = torch.empty(total_p * c, device=dev, dtype=torch.int32)
+    counts = torch.empty(v * c, device=dev, dtype=torch.int32)
+    row_off = torch.empty(v * c + 1, device=dev, dtype=torch.int32)
+    ws_bytes = int(lib.cdll.ssn_detections_batch_workspace_bytes(v, big_entries))
+    ws = torch.empty((ws_bytes + 3) // 4, device=dev, dtype=torch.int32)
+    lib.call("ssn_detections_batch", _p(act) if total_p else None, _p(comp) if total_p else None,
+             _p(rel_prop) if total_p else None, h_p_off.data_ptr(), _p(d_p_off), _p(report), _p(big_off.to(dev)), big_entries,
+             v, c, int(top_k), int(include_bg), float(nms_thresh), _p(combined) if total_p else None,
+             _p(kept) if total_p else None, _p(counts), _p(row_off), _p(ws), ws_bytes, _stream(lib, comp))
+    return combined, kept, row_off
+
+
+def detections_batch_fill(rel_prop, combined, reg, d_p_off, kept, row_off, n, regress):
+    """Stage fill (ssn_detections_batch_fill) for the n = row_off[-1] kept rows: -> rows [n, 5] fp64 (start, end, score, loc,
+    dur), cls, vid, prop [n] int32 on the device."""
+    lib = _check(rel_prop, combined, reg, d_p_off, kept, row_off)
+    total_p, c = combined.shape
+    v = d_p_off.numel() - 1
+    if reg is not None and (reg.shape != (total_p, c, 2) or reg.dtype != torch.float32):
+        raise ValueError("detections_batch_fill: reg must be float32 [P, C, 2]")
+    if row_off.shape != (v * c + 1,) or kept.shape != (total_p * c,) or rel_prop.shape != (total_p, 2):
+        raise ValueError("detections_batch_fill: tables of another batch")
+    dev = combined.device
+    n = int(n)
+    rows = torch.empty((n, 5), device=dev, dtype=torch.float64)
+    cls = torch.empty(n, device=dev, dtype=torch.int32)
+    vid = torch.empty(n, device=dev, dtype=torch.int32)
+    prop = torch.empty(n, device=dev, dtype=torch.int32)
+    lib.call("ssn_detections_batch_fill", _p(rel_prop) if n else None, _p(combined) if n else None,
+             _p(reg) if (n and reg is not None) else None, _p(d_p_off), _p(kept) if n else None, _p(row_off), v, c, total_p, n,
+             int(bool(regress)), _p(rows) if n else None, _p(cls) if n else None, _p(vid) if n else None,
+             _p(prop) if n else None, _stream(lib, combined))
+    return rows, cls, vid, prop
+
+
 def tag_count(scores, h_offsets, d_offsets, thresholds, bw, want_labels=False):
     """Counting phase of ssn_tag_count for a batch of videos: scores [N, 2] fp32 (the videos one after the other),
     h_offsets / d_offsets [V + 1] int32 (host / device copy), thresholds [n_thr] fp32 ->

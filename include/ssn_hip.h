@@ -368,6 +368,30 @@ size_t ssn_detections_workspace_bytes(int P, int C);
 int ssn_detections(const float* act, const float* comp, const float* reg, const double* rel_prop, float* combined,
                    double* dets, int* counts, void* workspace, size_t ws_bytes, int P, int C, int max_det, int top_k,
                    int include_bg, double nms_thresh, int regress, hipStream_t stream);
+/* The same for a BATCH of videos (csrc/detect_batch.hip): what eval_detection_results.py:91-178 runs video by video (the loop
+ * at :146-160 over the score dict) in a number of launches that does not depend on V, bit-identical to ssn_detections per
+ * video, ending in the flat rows ravel_detections (:188) forms.  The videos stand one after the other: act [total_p][C+1],
+ * comp [total_p][C], reg [total_p][C][2] or NULL (fp32), rel_prop [total_p][2] fp64, p_off [V + 1] int32 (given twice: a
+ * host copy that is validated before any launch, and the device copy the kernels read); report [V][C] uint8 or NULL: the
+ * classes a video reports (the --cls_scores branch, :130-144); a pair whose byte is 0 does no work and has no rows.  top_k and
+ * include_bg as above, top_k per video with flat indices counted inside the video.  total_p * C < 2^31.
+ *   batch       combined [total_p][C] fp32; kept [total_p * C] int32: the surviving proposals (index inside the video) of class
+ *               c of video v from p_off[v] * C + c * P_v on, in kept order; counts [V * C] int32; row_off [V * C + 1] int32 =
+ *               exclusive prefix sums of counts.  A video with P_v > 2048 sorts in the workspace: big_off [V + 1] int64
+ *               (device) = exclusive prefix sums of C * pow2(P_v) over those videos (nothing for the others), big_entries its
+ *               last entry; workspace: ssn_detections_batch_workspace_bytes(V, big_entries) bytes, 16-byte aligned.
+ *   batch_fill  after the caller's ONE host read, N = row_off[V * C]: rows [N][5] fp64 = (start, end, score, loc, dur), the
+ *               values ssn_detections writes into dets, and cls / vid / prop [N] int32 (prop: index inside the video), in the
+ *               order video, class ascending, kept order (descending score).
+ * The kernels bound every index they derive from the device tables. */
+size_t ssn_detections_batch_workspace_bytes(int V, long big_entries);
+int ssn_detections_batch(const float* act, const float* comp, const double* rel_prop, const int* h_p_off, const int* d_p_off,
+                         const unsigned char* report, const long* big_off, long big_entries, int V, int C, int top_k,
+                         int include_bg, double nms_thresh, float* combined, int* kept, int* counts, int* row_off,
+                         void* workspace, size_t ws_bytes, hipStream_t stream);
+int ssn_detections_batch_fill(const double* rel_prop, const float* combined, const float* reg, const int* p_off, const int* kept,
+                              const int* row_off, int V, int C, long total_p, long N, int regress, double* rows, int* cls,
+                              int* vid, int* prop, hipStream_t stream);
 
 /* Temporal actionness grouping for a BATCH of videos (csrc/tag.hip): gen_prop of gen_bottom_up_proposals.py:116-142, i.e.
  * label_frame_by_threshold (ops/sequence_funcs.py:11-34: fp32 softmax, scipy's gaussian_filter in fp64 with `reflect`

@@ -2,10 +2,10 @@
 """Evaluate detection results: score pickles in the ssn_test.py format + a proposal list -> the mAP table.
 
 The counterpart of the reference's eval_detection_results.py with the GPU stages of this project: the weighted merge of
-the pickles (detection_eval.merge_detection_scores), per video score fusion / top-k / NMS / regression
-(detection_post.DetectionPostProcessor, kept on the device), then one batched evaluation of all classes and thresholds
-(detection_eval.DetectionEvaluator).  Flags are named as the reference's; --num-class and --tiou stand in for its YAML
-lookup, --proposal-list for the list file the YAML names.
+the pickles (detection_eval.merge_detection_scores), score fusion / top-k / NMS / regression of all videos in one batched
+pass (detection_post.DetectionPostProcessor.process_videos; --per-video runs the same stage video by video), then one
+batched evaluation of all classes and thresholds (detection_eval.DetectionEvaluator).  Flags are named as the
+reference's; --num-class and --tiou stand in for its YAML lookup, --proposal-list for the list file the YAML names.
 
     python tools/eval_detections.py scores_rgb.pc scores_flow.pc --proposal-list data/thumos14_tag_test_normalized_proposal_list.txt \\
         --num-class 20 --tiou thumos14 --nms_threshold 0.2 --top_k 2000 --score_weights 1 1.2 --ap-out ap.npy
@@ -44,6 +44,8 @@ def main(argv=None):
     ap.add_argument("--score_weights", type=float, default=None, nargs="+")
     ap.add_argument("--ap-out", type=str, default=None, help="write the AP array [class, threshold] as .npy")
     ap.add_argument("--device", type=str, default=None)
+    ap.add_argument("--per-video", default=False, action="store_true",
+                    help="post-process video by video instead of all videos in one batched pass (same results; for A/B runs)")
     args = ap.parse_args(argv)
 
     import torch
@@ -72,13 +74,16 @@ def main(argv=None):
     post = DetectionPostProcessor(args.num_class, args.nms_threshold, args.top_k, args.no_regression, args.cls_top_k,
                                   args.softmax_before_filter)
     evaluator = DetectionEvaluator(args.num_class, thresholds, device=dev)
-    for vid, (rel_prop, act, comp, reg) in scores.items():
-        vcls = None if cls_scores is None else cls_scores[os.path.splitext(os.path.basename(vid))[0]]
-        dets, _ = post.process_video_device(np.asarray(rel_prop), torch.as_tensor(np.asarray(act)).to(dev),
-                                            torch.as_tensor(np.asarray(comp)).to(dev),
-                                            None if reg is None else torch.as_tensor(np.asarray(reg)).to(dev),
-                                            device=dev, video_cls_score=vcls)
-        evaluator.add_video(vid, dets)
+    vcls = None if cls_scores is None else {vid: cls_scores[os.path.splitext(os.path.basename(vid))[0]] for vid in scores}
+    if args.per_video:
+        for vid, (rel_prop, act, comp, reg) in scores.items():
+            dets, _ = post.process_video_device(np.asarray(rel_prop), torch.as_tensor(np.asarray(act)).to(dev),
+                                                torch.as_tensor(np.asarray(comp)).to(dev),
+                                                None if reg is None else torch.as_tensor(np.asarray(reg)).to(dev),
+                                                device=dev, video_cls_score=None if vcls is None else vcls[vid])
+            evaluator.add_video(vid, dets)
+    else:
+        evaluator.add_batch(post.process_videos(scores, device=dev, video_cls_scores=vcls))
     all_gt = ProposalSampler(args.proposal_list).all_gt()
     result = evaluator.evaluate(all_gt)
     if result.classes_without_gt:
