@@ -19,7 +19,7 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(_HERE, "libssn_hip.so")
-SOURCES = ["conv_igemm.hip", "conv_x6.hip", "conv_x6_rect.hip", "conv_wgrad.hip", "conv_wgrad_x6.hip", "elementwise.hip", "bn_train.hip", "frames.hip", "detect.hip", "detect_batch.hip", "pool.hip", "stpp.hip", "heads_losses.hip", "conv_pl.hip", "planes_ops.hip", "planes_bn.hip", "wgrad_pl.hip", "tag.hip", "eval.hip", "actionness.hip", "train_step.hip", "flow.hip", "jpeg.hip", "jpeg_encode.hip", "jpeg_transcode.hip", "video_cls.hip", "proposal_list.hip"]
+SOURCES = ["conv_igemm.hip", "conv_x6.hip", "conv_x6_rect.hip", "conv_wgrad.hip", "conv_wgrad_x6.hip", "elementwise.hip", "bn_train.hip", "frames.hip", "detect.hip", "detect_batch.hip", "pool.hip", "stpp.hip", "heads_losses.hip", "conv_pl.hip", "planes_ops.hip", "planes_bn.hip", "wgrad_pl.hip", "tag.hip", "eval.hip", "actionness.hip", "train_step.hip", "flow.hip", "jpeg.hip", "jpeg_encode.hip", "jpeg_transcode.hip", "video_cls.hip", "proposal_list.hip", "proposal_eval.hip"]
 
 STPP_MAX_PARTS = 24
 
@@ -84,6 +84,8 @@ _SIGS = {
     "ssn_sw_count": "pippipp",
     "ssn_sw_fill": "pippiipp",
     "ssn_proposal_list_rows": "ppippippipppp",
+    "ssn_proposal_eval_rank": "ppiiplpplp",
+    "ssn_proposal_eval_ar_an": "ppippiipppipidpppp",
     "ssn_vcls_status": "ppiiipp",
     "ssn_vcls_crop_reduce": "ppiiiip",
     "ssn_vcls_window_max": "pppppiiiiipp",
@@ -181,6 +183,7 @@ EXPORTS = sorted(list(_SIGS) + ["ssn_last_error", "ssn_abi_version", "ssn_conv_w
                                 "ssn_conv_debug_flags", "ssn_channel_sum_shares", "ssn_bn_train_workspace_floats",
                                 "ssn_conv_dgrad_layout", "ssn_conv_pl_tiles", "ssn_conv_pl_halo_taken", "ssn_conv_pl_debug_flags", "ssn_conv_pl_debug_trace", "ssn_conv_wgrad_pl_debug_trace", "ssn_conv_wgrad_pl_debug_flags", "ssn_conv_pl_tile_shape", "ssn_conv_wgrad_pl_tiles", "ssn_conv_wgrad_pl_workspace_bytes", "ssn_conv_wgrad_pl_group_workspace_bytes", "ssn_conv_wgrad_pl_group_table_bytes", "ssn_conv_wgrad_pl_group_tuning", "ssn_pl_channel_sum_workspace_bytes", "ssn_pl_bn_train_workspace_bytes", "ssn_conv_x6_pack_batch_entries", "ssn_conv_x6_pack_entry_bytes", "ssn_conv_x6_pack_batch_abort", "ssn_frames_resize_workspace_bytes", "ssn_frames_scale_workspace_bytes",
                                 "ssn_tag_workspace_bytes", "ssn_tag_lds_candidates", "ssn_eval_workspace_bytes", "ssn_eval_lds_gt",
+                                "ssn_proposal_eval_max_points", "ssn_proposal_eval_workspace_bytes",
                                 "ssn_vcls_lds_rows", "ssn_vcls_metrics_workspace_bytes",
                                 "ssn_sumsq_multi_workspace_floats", "ssn_train_step_launches"])
 
@@ -223,6 +226,10 @@ class SsnLibrary:
         self.cdll.ssn_eval_workspace_bytes.argtypes = [ctypes.c_long, ctypes.c_long, ctypes.c_int]
         self.cdll.ssn_eval_lds_gt.restype = ctypes.c_int
         self.cdll.ssn_eval_lds_gt.argtypes = []
+        self.cdll.ssn_proposal_eval_max_points.restype = ctypes.c_int
+        self.cdll.ssn_proposal_eval_max_points.argtypes = []
+        self.cdll.ssn_proposal_eval_workspace_bytes.restype = ctypes.c_size_t
+        self.cdll.ssn_proposal_eval_workspace_bytes.argtypes = [ctypes.c_long]
         self.cdll.ssn_vcls_lds_rows.restype = ctypes.c_int
         self.cdll.ssn_vcls_lds_rows.argtypes = []
         self.cdll.ssn_vcls_metrics_workspace_bytes.restype = ctypes.c_size_t
@@ -291,7 +298,7 @@ def build(force=False, verbose=False):
     a multi-GPU launch all call this)."""
     import fcntl
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
-    deps = srcs + [os.path.join(CSRC, h) for h in ("ssn_common.h", "conv_epilogue.h", "conv_x6_kernel.h", "planes.h", "conv_pl_epilogue.inc", "detect_common.h")]
+    deps = srcs + [os.path.join(CSRC, h) for h in ("ssn_common.h", "conv_epilogue.h", "conv_x6_kernel.h", "planes.h", "conv_pl_epilogue.inc", "detect_common.h", "eval_common.h")]
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
     stamp_path = LIB_PATH + ".stamp"
     want = _source_stamp(deps, flags)

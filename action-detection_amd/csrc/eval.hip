@@ -9,38 +9,14 @@
 // (class, threshold).  What is exact: the IoU is fp64 `inter / ((ge - gs) + (e - s) - inter)` in that order (no multiply,
 // nothing to contract; IEEE subtraction and division round as numpy's do), so the tp flags are numpy's; cumulative
 // counts are integers; a precision is one fp64 division of integers.  Only the final sum's order is this file's own.
-#include "ssn_common.h"
+#include "eval_common.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
 constexpr int EVAL_LDS_GT = 256;       // ground-truth rows of one (class, video) group matched out of LDS; more take the workspace
-constexpr int EVAL_SORT_LDS = 2048;    // entries of one class sorted inside LDS; more are sorted in place in the workspace
-constexpr int EVAL_MAX_T = 32;         // thresholds per call (one lane each in the matching wave)
-
-typedef unsigned long long u64;
-
-// total order on finite fp64 bit patterns (-0.0 counts as +0.0, as numpy compares them)
-__device__ __forceinline__ u64 eval_key(double s) {
-    const u64 b = __builtin_bit_cast(u64, s == 0.0 ? 0.0 : s);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-
-__device__ __forceinline__ bool eval_finite(double s) {
-    return (__builtin_bit_cast(u64, s) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
-}
-
-// the largest v with off[v] <= i (off non-decreasing, off[0] = 0 <= i < off[V])
-__device__ __forceinline__ int eval_find(const int* off, int V, int i) {
-    int lo = 0, hi = V - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= i) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
-}
+// (EVAL_SORT_LDS, EVAL_MAX_T, the score key, the offset search and the segment sort: eval_common.h)
 
 // rows per class; counts[C] = rows that cannot be evaluated (class out of range or score not finite)
 __global__ __launch_bounds__(256) void eval_count_kernel(const double* score, const int* cls, int n, int C, int* counts) {
@@ -64,52 +40,6 @@ __global__ __launch_bounds__(256) void eval_fill_kernel(const double* score, con
     if (sb < 0 || se > sort_entries || k < 0 || sb + k >= se) return;      // tables and rows disagree: drop the row
     hi[sb + k] = ~eval_key(score[i]);                                      // ascending ~key = descending score
     lo[sb + k] = ((u64)(uint32_t)i << 32) | (uint32_t)vid[i];
-}
-
-// One workgroup per class: bitonic sort of its pow2 segment, ascending on (hi, lo) -- descending score, then lower flat
-// index (the padding is all ones and stays behind).  Writes the class-wise order of the flat indices.
-__global__ __launch_bounds__(256) void eval_sort_kernel(u64* g_hi, u64* g_lo, const long* sort_off, long sort_entries,
-                                                        const int* pred_off, int N, int* order) {
-    __shared__ u64 l_hi[EVAL_SORT_LDS], l_lo[EVAL_SORT_LDS];
-    const int c = blockIdx.x, tid = threadIdx.x;
-    const long sb = sort_off[c], nl = sort_off[c + 1] - sb;
-    if (sb < 0 || nl <= 0 || sb + nl > sort_entries || nl > (1L << 30) || (nl & (nl - 1))) return;
-    const int n2 = (int)nl;
-    const bool in_lds = n2 <= EVAL_SORT_LDS;
-    u64* hi = in_lds ? l_hi : g_hi + sb;
-    u64* lo = in_lds ? l_lo : g_lo + sb;
-    if (in_lds) {
-        for (int i = tid; i < n2; i += 256) {
-            l_hi[i] = g_hi[sb + i];
-            l_lo[i] = g_lo[sb + i];
-        }
-    }
-    __syncthreads();
-    for (int k = 2; k <= n2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < n2; i += 256) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const bool asc = (i & k) == 0;
-                    const u64 hi_i = hi[i], hi_l = hi[l], lo_i = lo[i], lo_l = lo[l];
-                    const bool before = hi_i < hi_l || (hi_i == hi_l && lo_i < lo_l);      // i belongs first
-                    if (asc != before) {
-                        hi[i] = hi_l;
-                        hi[l] = hi_i;
-                        lo[i] = lo_l;
-                        lo[l] = lo_i;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    const int pb = pred_off[c], n = pred_off[c + 1] - pb;
-    if (pb < 0 || n < 0 || n > n2 || (long)pb + n > N) return;
-    for (int i = tid; i < n; i += 256) {
-        const u64 e = lo[i];
-        if (in_lds) g_lo[sb + i] = e;            // (the matching pass reads video and flat index from here)
-        order[pb + i] = (int)(e >> 32);
-    }
 }
 
 struct EvalMatchArgs {

@@ -1048,6 +1048,58 @@ def eval_recall(gt_span, gt_off, prop, prop_off, thresholds):
     return hits
 
 
+def proposal_eval_max_points():
+    return int(_lib.get_lib().cdll.ssn_proposal_eval_max_points())
+
+
+def proposal_eval_rank(score, prop_off, sort_off, sort_entries):
+    """ssn_proposal_eval_rank: score [P] fp64, prop_off [V + 1] int32, sort_off [V + 1] int64 (see include/ssn_hip.h) ->
+    order [P] int32: per video the flat indices in descending score, equal scores lower index first."""
+    lib = _check(score, prop_off, sort_off)
+    p, v = score.numel(), prop_off.numel() - 1
+    if score.shape != (p,) or score.dtype != torch.float64 or v < 1 or prop_off.shape != (v + 1,) or prop_off.dtype != torch.int32 \
+            or sort_off.shape != (v + 1,) or sort_off.dtype != torch.int64:
+        raise ValueError("proposal_eval_rank: score must be float64 [P], prop_off int32 [V + 1] and sort_off int64 [V + 1]")
+    sort_entries = int(sort_entries)
+    if sort_entries < p or sort_entries >= 2 ** 31:
+        raise ValueError("proposal_eval_rank: %d sort entries for %d proposals" % (sort_entries, p))
+    dev = prop_off.device
+    order = torch.zeros(p, device=dev, dtype=torch.int32)
+    ws_bytes = int(lib.cdll.ssn_proposal_eval_workspace_bytes(sort_entries))
+    ws = torch.zeros((ws_bytes + 7) // 8, device=dev, dtype=torch.int64)
+    lib.call("ssn_proposal_eval_rank", _p(score) if p else None, _p(prop_off), p, v, _p(sort_off), sort_entries,
+             _p(order) if p else None, _p(ws), ws_bytes, _stream(lib, prop_off))
+    return order
+
+
+def proposal_eval_ar_an(gt_span, gt_off, prop, prop_off, nr, thresholds, pcn, per_video, order=None):
+    """ssn_proposal_eval_ar_an: gt_span [G, 2] fp64, gt_off [V + 1] int32, prop [P, 2] fp64, prop_off [V + 1] int32, nr [V]
+    int32, thresholds [T] fp64, pcn [J] fp64, order [P] int32 or None -> (first_hit [G, T] int32, matches [T, J] int32,
+    curves [T * J + 2 J + 1] fp64 = recall, avg_recall, proposals_per_video, auc), all on the device."""
+    lib = _check(gt_span, gt_off, prop, prop_off, nr, thresholds, pcn, order)
+    g, p, v, t, j = gt_span.shape[0], prop.shape[0], gt_off.numel() - 1, thresholds.numel(), pcn.numel()
+    if gt_span.shape != (g, 2) or gt_span.dtype != torch.float64 or prop.shape != (p, 2) or prop.dtype != torch.float64 \
+            or gt_off.dtype != torch.int32 or prop_off.dtype != torch.int32 or prop_off.shape != gt_off.shape or v < 1 or g < 1:
+        raise ValueError("proposal_eval_ar_an: spans must be float64 [G >= 1, 2] / [P, 2], gt_off / prop_off int32 [V + 1]")
+    if nr.shape != (v,) or nr.dtype != torch.int32 or thresholds.dtype != torch.float64 or thresholds.dim() != 1 \
+            or pcn.dtype != torch.float64 or pcn.dim() != 1:
+        raise ValueError("proposal_eval_ar_an: nr must be int32 [V], thresholds and pcn float64 vectors")
+    if order is not None and (order.shape != (p,) or order.dtype != torch.int32):
+        raise ValueError("proposal_eval_ar_an: order must be int32 [P]")
+    if t < 1 or t > 32:
+        raise ValueError("proposal_eval_ar_an: between 1 and 32 tIoU thresholds in one call, got %d" % t)
+    if j < 1 or j > proposal_eval_max_points():
+        raise ValueError("proposal_eval_ar_an: between 1 and %d curve points in one call, got %d" % (proposal_eval_max_points(), j))
+    dev = thresholds.device
+    first_hit = torch.zeros((g, t), device=dev, dtype=torch.int32)
+    matches = torch.zeros((t, j), device=dev, dtype=torch.int32)
+    curves = torch.zeros(t * j + 2 * j + 1, device=dev, dtype=torch.float64)
+    lib.call("ssn_proposal_eval_ar_an", _p(gt_span), _p(gt_off), g, _p(prop) if p else None, _p(prop_off), p, v, _p(nr),
+             _p(order) if order is not None and p else None, _p(thresholds), t, _p(pcn), j, float(per_video), _p(first_hit),
+             _p(matches), _p(curves), _stream(lib, thresholds))
+    return first_hit, matches, curves
+
+
 # ------------------------------------------------------------------------------------ proposal lists
 def _sw_levels(spans, steps, who):
     """Host int32 arrays of the per-level span / step tables (kept alive by the caller for the duration of the call)."""

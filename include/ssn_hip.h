@@ -482,6 +482,32 @@ int ssn_proposal_list_rows(const double* gt_span, const int* gt_off, int G, cons
                            const int* frame_cnt, const double* durations, int V, int* gt_frames, int* frames, int* status,
                            hipStream_t stream);
 
+/* Proposal evaluation of a batch of videos (csrc/proposal_eval.hip): average recall against the average number of
+ * proposals per video (AR-AN), its area under the curve and recall against tIoU -- the ActivityNet toolkit's
+ * average_recall_vs_avg_nr_proposals, restated in DESIGN.md (the toolkit is the empty submodule named above).  The flat
+ * inputs are those of ssn_eval_recall; the proposals of a video are in rank order, best first, or `order` [P] int32 names
+ * them in that order (rank r of video v is row order[prop_off[v] + r]).  The host derives from the per-video counts alone
+ *   nr [V] int32    proposals of the video that exist after the truncation to max_avg_nr_proposals (0 without ground truth),
+ *   pcn [J] fp64    the ascending fractions of the curve points: at point j video v shows min(int(nr[v] * pcn[j]), nr[v]),
+ *   per_video       double(sum nr) / number of videos with ground truth.
+ *   rank    score [P] fp64 (finite; the caller checks), sort_off [V + 1] int64 = exclusive prefix sums of the videos'
+ *           proposal counts rounded up to a power of two (0 stays 0) -> order: per video descending score, equal scores
+ *           lower flat index first (the rule of ssn_eval_ap).  A video of up to 2048 proposals is sorted in LDS.
+ *   ar_an   first_hit [G][T] int32 = smallest rank r < nr[v] with tIoU(row, proposal) >= thresholds[t], -1 when none;
+ *           tIoU = inter / ((ge - gs) + (e - s) - inter) in fp64 in that order, as ssn_eval_ap.  matches [T][J] int32 =
+ *           rows whose first hit is shown at point j.  curves [T * J + 2 J + 1] fp64 = recall [T][J] (matches / G),
+ *           avg_recall [J] (mean over t), proposals_per_video [J] (pcn[j] * per_video), auc (trapezoid of avg_recall over
+ *           proposals_per_video, divided by its last entry).  A memset and two launches whatever V, G, P.
+ * T <= 32, J <= ssn_proposal_eval_max_points() (4096), G >= 1; refused on the host before any launch otherwise.  All
+ * pointers but the sizes are device memory; the kernels bound every index they derive from the device tables. */
+int ssn_proposal_eval_max_points(void);
+size_t ssn_proposal_eval_workspace_bytes(long sort_entries);
+int ssn_proposal_eval_rank(const double* score, const int* prop_off, int P, int V, const long* sort_off, long sort_entries,
+                           int* order, void* workspace, size_t ws_bytes, hipStream_t stream);
+int ssn_proposal_eval_ar_an(const double* gt_span, const int* gt_off, int G, const double* prop, const int* prop_off, int P,
+                            int V, const int* nr, const int* order, const double* thresholds, int T, const double* pcn, int J,
+                            double per_video, int* first_hit, int* matches, double* curves, hipStream_t stream);
+
 /* Video-level classification (csrc/video_cls.hip): the aggregation functions of ops/video_funcs.py and the metrics of
  * ops/metrics.py for a whole batch.  Rows of all videos one after the other, [N][C] fp32, ragged by offsets [V + 1] int32;
  * every pointer but the sizes is device memory and no call's launches depend on V.

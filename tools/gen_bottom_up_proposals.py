@@ -4,7 +4,7 @@ proposal list the trainers and the tester read.
 
 The counterpart of the reference's gen_bottom_up_proposals.py with the stages of this project chained on the GPU:
 tag_proposals.merge_scores -> TagProposalGenerator.generate (all videos in one batch) -> ProposalListBuilder.from_spans
--> ProposalListBuilder.build.  Flags are named as the reference's; --annotations stands in for its fixed data/ paths and
+-> ProposalListBuilder.build (-> proposal_eval.proposal_ar_an_batch with --ar_an, on the same device batch).  Flags are named as the reference's; --annotations stands in for its fixed data/ paths and
 --frame_path is used for both the folder lookup and the written paths (the reference hard-codes the former).  Not
 offered: --cls_scores and --iou_thresh (parsed there and never used), --reg_score_files (reaches an undefined name
 there).  Videos without instances are left out as in the reference, so its `allow_empty` case (ActivityNet `testing`)
@@ -38,6 +38,9 @@ def main(argv=None, db=None):
     ap.add_argument("--frame_path", type=str, default=None, help='folder of the frame folders (needed with --write_proposals)')
     ap.add_argument("--annotations", default=None, help="THUMOS14 annotation folder / ActivityNet JSON file")
     ap.add_argument("--device", type=str, default=None)
+    ap.add_argument("--ar_an", type=float, nargs='?', const=0.0, default=None, metavar='N',
+                    help='also print the AR-AN report (proposal_eval); N: the maximum average number of proposals per '
+                         'video, without a value the mean')
     args = ap.parse_args(argv)
     if args.write_proposals and not args.frame_path:
         ap.error("--write_proposals needs --frame_path")
@@ -95,6 +98,10 @@ def main(argv=None, db=None):
     for th, (pv, pi) in zip(thresholds, result.recall):
         print('IOU threshold {}. per video recall: {:02f}, per instance recall: {:02f}'.format(th, pv * 100, pi * 100))
     print('Average Recall: {:.04f} {:.04f}'.format(*(np.mean(result.recall, axis=0) * 100)))
+    if args.ar_an is not None:          # (TagResult.seconds is in NMS order, descending score: the batch's order is the rank)
+        from action_detection_amd.proposal_eval import format_ar_an_report, proposal_ar_an_batch
+        result.ar_an = proposal_ar_an_batch(batch, max_avg_nr_proposals=args.ar_an or None)
+        print(format_ar_an_report(result.ar_an))
 
     if args.write_proposals:
         bad = [v.id for v, s in zip(videos, result.status) if s]
