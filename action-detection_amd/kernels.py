@@ -1165,6 +1165,93 @@ def proposal_list_rows(gt_span, gt_off, prop, prop_off, frame_cnt, durations):
     return gt_frames, frames, status
 
 
+# ------------------------------------------------------------------------------------ test table
+TEST_TABLE_MAX_PARTS = 16
+_TEST_TABLE_BLOCK = 256
+
+
+def _test_table_inputs(who, frames, p_off, frame_cnt):
+    p, v = frames.shape[0], frame_cnt.numel()
+    if frames.shape != (p, 2) or frames.dtype != torch.int32:
+        raise ValueError("%s: frames must be int32 [P, 2], got %s %s" % (who, frames.dtype, tuple(frames.shape)))
+    if v < 1 or frame_cnt.shape != (v,) or frame_cnt.dtype != torch.int32 or p_off.shape != (v + 1,) or p_off.dtype != torch.int32:
+        raise ValueError("%s: frame_cnt must be int32 [V >= 1] and p_off int32 [V + 1]" % who)
+    if p >= 2 ** 30:
+        raise ValueError("%s: %d proposals in one batch (2^30 or more), split it" % (who, p))
+    return p, v
+
+
+def test_table_stages(stpp_cfg):
+    """The STPP configuration ``(starting, course, ending)`` (ints or tuples of ints) as the host arrays ssn_test_table_fill
+    takes: (levels per stage [3], parts per level, parts in total); more than 16 parts are refused."""
+    if len(stpp_cfg) != 3:
+        raise ValueError("test_table: the STPP configuration has three stages, got %r" % (stpp_cfg,))
+    stages = [(int(c),) if isinstance(c, int) else tuple(int(x) for x in c) for c in stpp_cfg]
+    parts = [x for st in stages for x in st]
+    if any(len(st) < 1 for st in stages) or min(parts) < 1:
+        raise ValueError("test_table: every stage needs at least one level of at least one part, got %r" % (stpp_cfg,))
+    if sum(parts) > TEST_TABLE_MAX_PARTS:
+        raise ValueError("test_table: %d parts in total, at most %d supported" % (sum(parts), TEST_TABLE_MAX_PARTS))
+    return [len(st) for st in stages], parts, sum(parts)
+
+
+test_table_stages.__test__ = False      # (library functions whose names start with "test": not test cases)
+
+
+def test_table_mark(frames, p_off, frame_cnt):
+    """ssn_test_table_mark: frames [P, 2] int32, p_off [V + 1] int32, frame_cnt [V] int32 (device) -> (keep [P], pre [P],
+    bp [ceil(P / 256) + 1], counts [V]) int32: the keep flags, their prefix sums, and the rows of every video in the table
+    (-1: the video holds a negative frame number)."""
+    lib = _check(frames, p_off, frame_cnt)
+    p, v = _test_table_inputs("test_table_mark", frames, p_off, frame_cnt)
+    dev = frame_cnt.device
+    # (every element is written: keep / pre by the lane of their row, bp by its block and the scan, counts by the entry's memset)
+    keep = torch.empty(p, device=dev, dtype=torch.int32)
+    pre = torch.empty(p, device=dev, dtype=torch.int32)
+    bp = torch.empty((p + _TEST_TABLE_BLOCK - 1) // _TEST_TABLE_BLOCK + 1, device=dev, dtype=torch.int32)
+    counts = torch.empty(v, device=dev, dtype=torch.int32)
+    lib.call("ssn_test_table_mark", _p(frames) if p else None, _p(p_off), p, _p(frame_cnt), v, _p(keep) if p else None,
+             _p(pre) if p else None, _p(bp), _p(counts), _stream(lib, frame_cnt))
+    return keep, pre, bp, counts
+
+
+test_table_mark.__test__ = False
+
+
+def test_table_fill(frames, p_off, frame_cnt, n_rows, keep, pre, bp, k_off, total, stpp_cfg):
+    """ssn_test_table_fill: the inputs and outputs of ``test_table_mark``, n_rows [V] int32, k_off [V + 1] int32 (device;
+    exclusive prefix sums of the counts, last entry ``total``) and the STPP configuration (host) -> (src [K] int32, rel
+    [K, 2] fp64, ticks [K, 4] int32, scaling [K, 2] fp64, ranges [K, n_parts, 2] int32, act [K, 2] int32)."""
+    lib = _check(frames, p_off, frame_cnt, n_rows, keep, pre, bp, k_off)
+    p, v = _test_table_inputs("test_table_fill", frames, p_off, frame_cnt)
+    stage_entries, parts, n_parts = test_table_stages(stpp_cfg)
+    total = int(total)
+    if n_rows.shape != (v,) or n_rows.dtype != torch.int32 or k_off.shape != (v + 1,) or k_off.dtype != torch.int32:
+        raise ValueError("test_table_fill: n_rows must be int32 [V] and k_off int32 [V + 1]")
+    if keep.shape != (p,) or pre.shape != (p,) or bp.numel() != (p + _TEST_TABLE_BLOCK - 1) // _TEST_TABLE_BLOCK + 1 \
+            or any(t.dtype != torch.int32 for t in (keep, pre, bp)):
+        raise ValueError("test_table_fill: keep / pre / bp are not the outputs of test_table_mark for these frames")
+    if total < v or total > p + v:
+        raise ValueError("test_table_fill: %d rows for %d videos and %d proposals" % (total, v, p))
+    dev = frame_cnt.device
+    src = torch.zeros(total, device=dev, dtype=torch.int32)
+    rel = torch.zeros((total, 2), device=dev, dtype=torch.float64)
+    ticks = torch.zeros((total, 4), device=dev, dtype=torch.int32)
+    scaling = torch.zeros((total, 2), device=dev, dtype=torch.float64)
+    ranges = torch.zeros((total, n_parts, 2), device=dev, dtype=torch.int32)
+    act = torch.zeros((total, 2), device=dev, dtype=torch.int32)
+    h_stage = (ctypes.c_int * 3)(*stage_entries)
+    h_parts = (ctypes.c_int * len(parts))(*parts)
+    lib.call("ssn_test_table_fill", _p(frames) if p else None, _p(p_off), p, _p(frame_cnt), _p(n_rows), v,
+             _p(keep) if p else None, _p(pre) if p else None, _p(bp), _p(k_off), total, ctypes.addressof(h_stage),
+             ctypes.addressof(h_parts), len(parts), _p(src), _p(rel), _p(ticks), _p(scaling), _p(ranges), _p(act),
+             _stream(lib, frame_cnt))
+    return src, rel, ticks, scaling, ranges, act
+
+
+test_table_fill.__test__ = False
+
+
 # ------------------------------------------------------------------------------------ video-level classification
 def vcls_lds_rows():
     return int(_lib.get_lib().cdll.ssn_vcls_lds_rows())

@@ -93,7 +93,8 @@ class STPPReorgainzed:
 
     The per-proposal row ranges are computed on the host with the reference's own float
     arithmetic (np.arange + int(), :137-147) -- a few hundred integers per video -- and the
-    pooling itself is one launch with one workgroup per proposal.
+    pooling itself is one launch with one workgroup per proposal.  ``forward_ranges`` takes the ranges from the device instead
+    (csrc/test_table.hip forms them for all videos of a batch at once).
     """
 
     def __init__(self, feat_dim, act_score_len, comp_score_len, reg_score_len,
@@ -170,13 +171,26 @@ class STPPReorgainzed:
             np.minimum(act[:, 1], t_rows, out=act[:, 1])
             ranges[live & (ranges[..., 0] >= t_rows)] = -1
             act[act[:, 0] >= t_rows] = -1
+        return self.forward_ranges(scores, torch.from_numpy(ranges).to(dev), torch.from_numpy(act).to(dev), scaling)
+
+    def forward_ranges(self, scores, ranges, act, scaling):
+        """The pooling itself, from row ranges that are on the device already: ``ranges`` int32 [P, n_parts, 2] and ``act``
+        int32 [P, 2] as ``forward`` forms them (``host_ranges`` + its clamps) or as ``ssn_test_table_fill`` writes them;
+        ``scaling`` [P, 2] of any float type, rounded to float32 here.  Nothing is read back."""
+        assert scores.size(1) == self.feat_dim
+        dev = scores.device
+        n_out = ranges.size(0)
+        if ranges.dtype != torch.int32 or act.dtype != torch.int32 or tuple(ranges.shape[1:]) != (self.feat_multiplier, 2) \
+                or tuple(act.shape) != (n_out, 2):
+            raise ValueError("forward_ranges: ranges must be int32 [P, %d, 2] and act int32 [P, 2], got %s %s / %s %s"
+                             % (self.feat_multiplier, ranges.dtype, tuple(ranges.shape), act.dtype, tuple(act.shape)))
+        ranges_d, act_d = ranges.to(dev).contiguous(), act.to(dev).contiguous()
         sc = scaling if torch.is_tensor(scaling) else torch.as_tensor(np.asarray(scaling))
         sc = sc.to(device=dev, dtype=torch.float32).reshape(-1, 2).contiguous()
         out_act = torch.empty((n_out, self.act_len), device=dev, dtype=torch.float32)
         out_comp = torch.empty((n_out, self.comp_len), device=dev, dtype=torch.float32)
         out_reg = torch.empty((n_out, self.reg_len), device=dev, dtype=torch.float32) if self.with_regression else None
         scores = scores.contiguous().float()
-        ranges_d, act_d = torch.from_numpy(ranges).to(dev), torch.from_numpy(act).to(dev)
         cols = torch.tensor(self._part_cols, dtype=torch.int32, device=dev)
         if self.sc:
             K.stpp_reorg(scores, ranges_d, act_d, sc, cols, self.act_len, self.comp_len, self.reg_len, out_act, out_comp, out_reg)

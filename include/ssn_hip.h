@@ -482,6 +482,31 @@ int ssn_proposal_list_rows(const double* gt_span, const int* gt_off, int G, cons
                            const int* frame_cnt, const double* durations, int V, int* gt_frames, int* frames, int* status,
                            hipStream_t stream);
 
+/* The test table of a batch of videos (csrc/test_table.hip): from the frame-number columns of a proposal list to what the
+ * dense tester needs per proposal -- the rows ProposalSampler.test_ticks forms (ssn_dataset.py:393-428) and the row ranges
+ * STPPReorgainzed computes from them (ops/ssn_ops.py:125-157), for all videos at once.  frames [P][2] int32 (start, end),
+ * ragged by p_off [V + 1] int32; frame_cnt [V] and n_rows [V] int32 (n_rows: the ticks of the video, len(arange(0,
+ * frame_cnt - new_length, test_interval)), formed by the caller; the caller refuses frame_cnt < 2 and n_rows < 1).
+ *   mark   keep [P] int32: end > start and start < frame_cnt (the two filters of a list record); pre [P] and bp
+ *          [ceil(P / 256) + 1] int32: prefix sums of keep inside blocks of 256 rows and over the blocks; counts [V] int32:
+ *          rows of the video in the table = kept proposals, 1 when there is none (the whole-video row (0, frame_cnt - 1)),
+ *          -1 when the video holds a negative frame number.  ONE host read of counts sizes the table: k_off [V + 1] int32
+ *          are their exclusive prefix sums, K the total.
+ *   fill   the kept rows compacted in input order: src [K] int32 (index inside the video's input, -1: whole-video row),
+ *          rel [K][2] fp64 (start / frame_cnt, min(end, frame_cnt) / frame_cnt), ticks [K][4] int32 and scaling [K][2] fp64
+ *          as test_ticks forms them (every expression one fp64 operation, truncation toward zero), ranges [K][n_parts][2]
+ *          and act [K][2] int32 as STPPReorgainzed.forward hands them to ssn_stpp_reorg: (0, 0) a skipped part, ends cut
+ *          at n_rows, (-1, -1) a range that starts at or behind n_rows.  The STPP configuration comes from the HOST:
+ *          h_stage_entries [3] pyramid levels per stage, h_parts [n_entries] parts per level, at most 16 parts in total.
+ * Launches do not depend on V; no atomic decides a position (two runs write the same bytes); every index derived from a
+ * device table is bounded.  All pointers but h_stage_entries / h_parts are device memory. */
+int ssn_test_table_mark(const int* frames, const int* p_off, int P, const int* frame_cnt, int V, int* keep, int* pre, int* bp,
+                        int* counts, hipStream_t stream);
+int ssn_test_table_fill(const int* frames, const int* p_off, int P, const int* frame_cnt, const int* n_rows, int V,
+                        const int* keep, const int* pre, const int* bp, const int* k_off, int K, const int* h_stage_entries,
+                        const int* h_parts, int n_entries, int* src, double* rel, int* ticks, double* scaling, int* ranges,
+                        int* act, hipStream_t stream);
+
 /* Proposal evaluation of a batch of videos (csrc/proposal_eval.hip): average recall against the average number of
  * proposals per video (AR-AN), its area under the curve and recall against tIoU -- the ActivityNet toolkit's
  * average_recall_vs_avg_nr_proposals, restated in DESIGN.md (the toolkit is the empty submodule named above).  The flat

@@ -83,6 +83,19 @@ def device_transform(net, modality, device, input_size=None, scale=False, index=
     return transform
 
 
+def build_net(modality, weights, arch="BNInception", device="cuda:0"):
+    """The trained ``BinaryClassifier`` of a checkpoint, ready for ``ActionnessTester`` on ``device``."""
+    import torch
+    from action_detection_amd.binary_model import BinaryClassifier
+    data_length = 1 if modality == "RGB" else 5
+    net = BinaryClassifier(2, 5, modality, test_mode=True, new_length=data_length, base_model=arch)
+    checkpoint = torch.load(weights, map_location="cpu")
+    print("model epoch {} loss: {}".format(checkpoint.get('epoch'), checkpoint.get('best_loss')))
+    net.load_state_dict({'.'.join(k.split('.')[1:]): v for k, v in checkpoint['state_dict'].items()})
+    net.prepare_test_fc()
+    return net.to(device).eval()
+
+
 def extract(net, sampler, load, test_crops=10, input_size=None, tick_batch=32, grouping="reference", max_num=-1, verbose=True,
             transform=None):
     """-> ActionnessScores of the first max_num (all) videos of the sampler's list; ``net`` as ActionnessTester takes it.
@@ -139,18 +152,11 @@ def main(argv=None):
     ap.add_argument("--gpu-scale", action="store_true", help="with --gpu-decode: frames of any size, GroupScale on the device")
     args = ap.parse_args(argv)
 
-    import torch
     import action_detection_amd as pkg
     from action_detection_amd.actionness_sampling import ActionnessSampler
-    from action_detection_amd.binary_model import BinaryClassifier
     pkg.build()
     data_length = 1 if args.modality == "RGB" else 5
-    net = BinaryClassifier(2, 5, args.modality, test_mode=True, new_length=data_length, base_model=args.arch)
-    checkpoint = torch.load(args.weights, map_location="cpu")
-    print("model epoch {} loss: {}".format(checkpoint.get('epoch'), checkpoint.get('best_loss')))
-    net.load_state_dict({'.'.join(k.split('.')[1:]): v for k, v in checkpoint['state_dict'].items()})
-    net.prepare_test_fc()
-    net.to(args.device).eval()
+    net = build_net(args.modality, args.weights, args.arch, args.device)
     sampler = ActionnessSampler(args.proposal_list, new_length=data_length, test_interval=args.frame_interval)
     if args.gpu_decode:
         scores = extract(net, sampler, file_reader(args.frame_root, args.modality, args.flow_pref), args.test_crops, args.input_size,
