@@ -161,6 +161,7 @@ _SIGS = {
     "ssn_conv_wgrad_pl": "ppppppiiiiliiiliiiiiplippiipp",
     "ssn_wgrad_reduce_multi": "ipppppppp",
     "ssn_conv_wgrad_pl_group": "ippppppppppplplp",
+    "ssn_conv_wgrad_pl_group_lanes": "ippppppppppplplp" + "pii",
     "ssn_conv_pl_dgrad_s2": "pppppiiiiliiiliiplpipppp",
     "ssn_pl_maxpool_fwd": "pplpplpiiiiiiiiipppp",
     "ssn_pl_maxpool_bwd": "pplpppl" + "i" * 10 + "plpipppplp",

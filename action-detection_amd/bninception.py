@@ -208,6 +208,11 @@ class BNInception(nn.Module):
         # scales are the previous step's.
         self.branch_lanes = os.environ.get("SSN_BRANCH_LANES", "1") != "0"
         self._side_streams = {}
+        # planes_exec: the grouped weight gradients with every family's slabs summed right behind its kernel and the families on
+        # three side streams of their own, forked and joined inside the call (ssn_conv_wgrad_pl_group_lanes).  Bit-identical
+        # results.  Measured (profiles/wgrad_lanes_measured.txt): -0.11 ... -0.17 ms per step on three boxes.  0: one stream, one reduction at the end; the
+        # streams are also off whenever overlap_wgrad or branch_lanes is cleared (bench.py --single-stream).
+        self.wgrad_lanes = os.environ.get("SSN_WGRAD_LANES", "1") != "0"
         self.infer_cache = os.environ.get("SSN_INFER_CACHE", "1") != "0"   # planes_exec: packed weights / folded BN reused across no-grad forwards
         self.pooled_mask = os.environ.get("SSN_POOLED_MASK", "1") != "0"   # planes_exec: stem pools' backward reads the pooled sign
         # planes_exec: all weight operands of a pass packed in three launches through a device-resident plan (kernels.PackBatch)
@@ -808,6 +813,13 @@ class BNInception(nn.Module):
         if st is None:
             st = self._side_streams[dev] = torch.cuda.Stream(device=dev)
         return st
+
+    def _wgrad_streams(self, dev, count):
+        """`count` side streams for the families of a grouped weight-gradient call (none of them a block lane's stream)."""
+        sts = self.__dict__.setdefault("_wg_streams", {}).setdefault(dev, [])
+        while len(sts) < count:
+            sts.append(torch.cuda.Stream(device=dev))
+        return sts[:count]
 
     def _wgrad_group_buffers(self, jobs, dev):
         """(workspace, table) of a grouped weight-gradient call: persistent buffers, grown on demand (planes_exec.run_backward)."""

@@ -24,6 +24,8 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <map>
+#include <mutex>
 #include <vector>
 
 namespace {
@@ -1144,6 +1146,7 @@ struct WgGroupItem {
     int kg;                // partial slabs per split
     int taps;              // tap-major slabs (nine-tap bodies): 9, else 1
     long ws_off;           // byte offset of the problem's slabs in the workspace
+    int pin;               // units per split given by the caller (shape[15]; 0: the planner chooses)
     float* dw;
     float* db;
 };
@@ -1281,6 +1284,9 @@ void plan_group(std::vector<WgGroupItem*>& fam, int slots, double fixed_cost, in
         long per = (long)(target / it->unit_cost + 0.5);
         const long floor_units = (it->family >= WGF_1 && it->chunked) ? (min_units + 3) / 4 : min_units;   // (a chunk = 4 k-steps)
         if (per < floor_units) per = floor_units;
+        // a pinned share (a PART of a pass's problems keeps the plan of the whole pass: a part planned by itself has less work per
+        // family, so it would be split further -- a lone small problem to fill every slot -- and sum in another order)
+        if (it->pin > 0) per = it->pin;
         if (per > it->units) per = it->units;
         long splits = (it->units + per - 1) / per;
         per = (it->units + splits - 1) / splits;           // (equal shares)
@@ -1361,6 +1367,8 @@ int plan_group_all(int count, const int* shape, const long* groups, const void* 
         if (rc != SSN_OK) return rc;
         it.dw = dw ? dw[i] : nullptr;
         it.db = db ? db[i] : nullptr;
+        SSN_CHECK_ARG(sh[15] >= 0, "conv wgrad pl group: problem %d: units per split %d", i, sh[15]);
+        it.pin = sh[15];
         rc = classify_group(it, sh[14]);
         if (rc != SSN_OK) return rc;
     }
@@ -1413,10 +1421,46 @@ extern "C" long ssn_conv_wgrad_pl_group_workspace_bytes(int count, const int* sh
 extern "C" int ssn_wgrad_reduce_multi(int count, const float* const* part, float* const* dw, float* const* db, const int* M,
                                       const int* K, const int* splits, const int* taps, hipStream_t stream);
 
-extern "C" int ssn_conv_wgrad_pl_group(int count, const void* const* g_hi, const void* const* g_lo, const void* const* x_hi,
-                                       const void* const* x_lo, float* const* dw, float* const* db, const int* shape,
-                                       const long* groups, const float* const* g_scale, const float* const* x_scale, void* workspace,
-                                       long ws_bytes, void* table, long table_bytes, hipStream_t stream) {
+namespace {
+constexpr int WGL_MAX = 8;      // side streams a grouped call fans its families out over, at most
+#if defined(__HIP__)
+// Fork / join events of the fan-out: created once per device (no timing), outside any capture, and reused by every call -- an
+// event only carries the position it was last recorded at, and a wait reads it when the wait is issued.
+struct WgLaneEvents {
+    hipEvent_t fork;
+    hipEvent_t join[WGL_MAX];
+};
+WgLaneEvents* wgrad_lane_events(hipStream_t stream) {
+    static std::mutex mu;
+    static std::map<int, WgLaneEvents> cache;
+    std::lock_guard<std::mutex> lock(mu);
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+    auto it = cache.find(dev);
+    if (it != cache.end()) return &it->second;
+    hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &status) != hipSuccess || status != hipStreamCaptureStatusNone) {
+        (void)hipGetLastError();
+        return nullptr;      // (no events yet and the stream is capturing: this call keeps to one stream)
+    }
+    WgLaneEvents ev;
+    bool ok = hipEventCreateWithFlags(&ev.fork, hipEventDisableTiming) == hipSuccess;
+    for (int k = 0; k < WGL_MAX && ok; ++k) ok = hipEventCreateWithFlags(&ev.join[k], hipEventDisableTiming) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    return &cache.emplace(dev, ev).first->second;
+}
+#endif
+
+// The grouped call.  per_family: the slabs of a family are summed right behind its kernel (families in the order of their slab
+// bytes, largest first) instead of by one reduction at the end.  lanes / n_lanes: family k and its reduction run on lanes[k % n_lanes],
+// forked behind the table writes of the calling stream; join: the calling stream waits for every lane before the call returns.
+int wgrad_group_run(int count, const void* const* g_hi, const void* const* g_lo, const void* const* x_hi, const void* const* x_lo,
+                    float* const* dw, float* const* db, const int* shape, const long* groups, const float* const* g_scale,
+                    const float* const* x_scale, void* workspace, long ws_bytes, void* table, long table_bytes, hipStream_t stream,
+                    bool per_family, const hipStream_t* lanes, int n_lanes, bool join) {
     if (count == 0) return SSN_OK;
     SSN_CHECK_ARG(count > 0 && g_hi && g_lo && x_hi && x_lo && dw && db && shape && groups && g_scale && x_scale && workspace && table,
                   "conv wgrad pl group: null pointer");
@@ -1433,7 +1477,16 @@ extern "C" int ssn_conv_wgrad_pl_group(int count, const void* const* g_hi, const
         ssn_set_error("conv wgrad pl group: table %ld < %ld bytes", table_bytes, ssn_conv_wgrad_pl_group_table_bytes(count));
         return SSN_ERR_WORKSPACE;
     }
+    SSN_CHECK_ARG(n_lanes >= 0 && n_lanes <= WGL_MAX && (n_lanes == 0 || (lanes && per_family)), "conv wgrad pl group: %d side streams",
+                  n_lanes);
+    for (int k = 0; k < n_lanes; ++k) SSN_CHECK_ARG(lanes[k] && lanes[k] != stream, "conv wgrad pl group: side stream %d", k);
     WgGroupEntry* dev = static_cast<WgGroupEntry*>(table);
+    struct Launch {
+        int family, first;      // first: table position of its problems
+        std::vector<WgGroupItem*> items;
+        long slab_bytes;
+    };
+    std::vector<Launch> launches;
     int first = 0;      // table position of the next launch's problems
     for (int f = 0; f < WGF_COUNT; ++f) {
         std::vector<WgGroupItem*> fam;
@@ -1464,54 +1517,160 @@ extern "C" int ssn_conv_wgrad_pl_group(int count, const void* const* g_hi, const
         }
         for (size_t base = 0; base < fam.size(); base += WGG_MAX) {
             const int n = (int)std::min<size_t>(WGG_MAX, fam.size() - base);
-            WgGroupIndex ix;
-            ix.count = n;
-            long blocks = 0;
-            for (int c0 = 0; c0 < n; c0 += WGG_WRITE) {
-                WgGroupChunk ch;
-                ch.count = std::min(WGG_WRITE, n - c0);
-                for (int j = 0; j < ch.count; ++j) {
-                    WgGroupItem& it = *fam[base + (size_t)(c0 + j)];
-                    it.a.part = reinterpret_cast<float*>(static_cast<char*>(workspace) + it.ws_off);
-                    ch.e[j].a = it.a;
-                    ch.e[j].variant = it.variant;
-                    ch.e[j].nblk = (uint32_t)(it.tiles * it.a.splits);
-                    ix.blk0[c0 + j] = (int)blocks;
-                    blocks += (it.tiles * it.a.splits + 7) / 8 * 8;
-                }
-                hipLaunchKernelGGL(wgrad_group_write_kernel, dim3(1), dim3(64), 0, stream, ch, dev, first + c0);
-            }
-            SSN_CHECK_ARG(blocks < (1l << 31), "conv wgrad pl group: too many blocks");
-            for (int j = n; j <= WGG_MAX; ++j) ix.blk0[j] = (int)blocks;
-            const WgGroupEntry* tab = dev + first;
-            switch (f) {
-                case WGF_9_XP6: hipLaunchKernelGGL((wgrad_group9_kernel<6, 1>), dim3((unsigned)blocks), dim3(256), 0, stream, tab, ix); break;
-                case WGF_9_XP8: hipLaunchKernelGGL((wgrad_group9_kernel<8, 2>), dim3((unsigned)blocks), dim3(512), 0, stream, tab, ix); break;
-                case WGF_9_XP12: hipLaunchKernelGGL((wgrad_group9_kernel<12, 2>), dim3((unsigned)blocks), dim3(512), 0, stream, tab, ix); break;
-                case WGF_STEM: hipLaunchKernelGGL(wgrad_group_stem_kernel, dim3((unsigned)blocks), dim3(512), 0, stream, tab, ix); break;
-                case WGF_7_ROW: hipLaunchKernelGGL((wgrad_group9_kernel<6, 1, 1, 7>), dim3((unsigned)blocks), dim3(256), 0, stream, tab, ix); break;
-                case WGF_7_COL: hipLaunchKernelGGL((wgrad_group9_kernel<12, 2, 7, 1>), dim3((unsigned)blocks), dim3(512), 0, stream, tab, ix); break;
-                default: hipLaunchKernelGGL(wgrad_group1_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, tab, ix); break;
-            }
+            Launch L;
+            L.family = f;
+            L.first = first;
+            L.items.assign(fam.begin() + (long)base, fam.begin() + (long)base + n);
+            L.slab_bytes = 0;
+            for (const WgGroupItem* it : L.items) L.slab_bytes += (long)it->a.splits * it->kg * it->a.M * it->a.ldp * (long)sizeof(float);
+            launches.push_back(std::move(L));
             first += n;
         }
     }
-    SSN_CHECK_LAUNCH("conv_wgrad_pl_group");
-    // the reduction of every problem's slabs, in the fixed order of the single launches
-    std::vector<const float*> parts((size_t)count);
-    std::vector<float*> dws((size_t)count), dbs((size_t)count);
-    std::vector<int> Ms((size_t)count), Ks((size_t)count), sp((size_t)count), tp((size_t)count);
-    for (int i = 0; i < count; ++i) {
-        const WgGroupItem& it = items[(size_t)i];
-        parts[(size_t)i] = reinterpret_cast<const float*>(static_cast<char*>(workspace) + it.ws_off);
-        dws[(size_t)i] = it.dw;
-        dbs[(size_t)i] = it.db;
-        Ms[(size_t)i] = it.a.M;
-        Ks[(size_t)i] = it.a.K;
-        sp[(size_t)i] = it.a.splits * it.kg;
-        tp[(size_t)i] = it.taps;
+    // per-family reductions: the family with the most slab bytes first -- its sum then runs under the longest stretch of the
+    // launches behind it, and only the smallest family's sum stays exposed at the end (ties: the family order)
+    if (per_family)
+        std::stable_sort(launches.begin(), launches.end(), [](const Launch& x, const Launch& y) { return x.slab_bytes > y.slab_bytes; });
+
+    int fan = n_lanes;
+#if defined(__HIP__)
+    WgLaneEvents* ev = fan > 0 ? wgrad_lane_events(stream) : nullptr;
+    if (!ev) fan = 0;
+#else
+    SSN_CHECK_ARG(n_lanes == 0, "conv wgrad pl group: the host build has no streams");
+#endif
+
+    // the problems of a launch into the table (always on the calling stream) -> its grid and block -> problem index
+    auto write_table = [&](const Launch& L, WgGroupIndex& ix) -> long {
+        const int n = (int)L.items.size();
+        ix.count = n;
+        long blocks = 0;
+        for (int c0 = 0; c0 < n; c0 += WGG_WRITE) {
+            WgGroupChunk ch;
+            ch.count = std::min(WGG_WRITE, n - c0);
+            for (int j = 0; j < ch.count; ++j) {
+                WgGroupItem& it = *L.items[(size_t)(c0 + j)];
+                it.a.part = reinterpret_cast<float*>(static_cast<char*>(workspace) + it.ws_off);
+                ch.e[j].a = it.a;
+                ch.e[j].variant = it.variant;
+                ch.e[j].nblk = (uint32_t)(it.tiles * it.a.splits);
+                ix.blk0[c0 + j] = (int)blocks;
+                blocks += (it.tiles * it.a.splits + 7) / 8 * 8;
+            }
+            hipLaunchKernelGGL(wgrad_group_write_kernel, dim3(1), dim3(64), 0, stream, ch, dev, L.first + c0);
+        }
+        for (int j = n; j <= WGG_MAX; ++j) ix.blk0[j] = (int)blocks;
+        return blocks;
+    };
+    auto launch_family = [&](const Launch& L, const WgGroupIndex& ix, long blocks, hipStream_t s) {
+        const WgGroupEntry* tab = dev + L.first;
+        switch (L.family) {
+            case WGF_9_XP6: hipLaunchKernelGGL((wgrad_group9_kernel<6, 1>), dim3((unsigned)blocks), dim3(256), 0, s, tab, ix); break;
+            case WGF_9_XP8: hipLaunchKernelGGL((wgrad_group9_kernel<8, 2>), dim3((unsigned)blocks), dim3(512), 0, s, tab, ix); break;
+            case WGF_9_XP12: hipLaunchKernelGGL((wgrad_group9_kernel<12, 2>), dim3((unsigned)blocks), dim3(512), 0, s, tab, ix); break;
+            case WGF_STEM: hipLaunchKernelGGL(wgrad_group_stem_kernel, dim3((unsigned)blocks), dim3(512), 0, s, tab, ix); break;
+            case WGF_7_ROW: hipLaunchKernelGGL((wgrad_group9_kernel<6, 1, 1, 7>), dim3((unsigned)blocks), dim3(256), 0, s, tab, ix); break;
+            case WGF_7_COL: hipLaunchKernelGGL((wgrad_group9_kernel<12, 2, 7, 1>), dim3((unsigned)blocks), dim3(512), 0, s, tab, ix); break;
+            default: hipLaunchKernelGGL(wgrad_group1_kernel, dim3((unsigned)blocks), dim3(256), 0, s, tab, ix); break;
+        }
+    };
+    // the reduction of the given problems' slabs, each in the fixed order of the single launches
+    auto reduce = [&](const std::vector<const WgGroupItem*>& its, hipStream_t s) -> int {
+        const size_t n = its.size();
+        std::vector<const float*> parts(n);
+        std::vector<float*> dws(n), dbs(n);
+        std::vector<int> Ms(n), Ks(n), sp(n), tp(n);
+        for (size_t i = 0; i < n; ++i) {
+            const WgGroupItem& it = *its[i];
+            parts[i] = reinterpret_cast<const float*>(static_cast<char*>(workspace) + it.ws_off);
+            dws[i] = it.dw;
+            dbs[i] = it.db;
+            Ms[i] = it.a.M;
+            Ks[i] = it.a.K;
+            sp[i] = it.a.splits * it.kg;
+            tp[i] = it.taps;
+        }
+        return ssn_wgrad_reduce_multi((int)n, parts.data(), dws.data(), dbs.data(), Ms.data(), Ks.data(), sp.data(), tp.data(), s);
+    };
+
+    std::vector<WgGroupIndex> index(launches.size());
+    std::vector<long> grid(launches.size());
+    if (fan > 0) {
+        // every table entry first: the lanes fork behind all of them
+        for (size_t k = 0; k < launches.size(); ++k) {
+            grid[k] = write_table(launches[k], index[k]);
+            SSN_CHECK_ARG(grid[k] < (1l << 31), "conv wgrad pl group: too many blocks");
+        }
+        SSN_CHECK_LAUNCH("conv_wgrad_pl_group");
     }
-    return ssn_wgrad_reduce_multi(count, parts.data(), dws.data(), dbs.data(), Ms.data(), Ks.data(), sp.data(), tp.data(), stream);
+#if defined(__HIP__)
+    if (fan > 0) {
+        bool ok = hipEventRecord(ev->fork, stream) == hipSuccess;
+        for (int k = 0; k < fan && ok; ++k) ok = hipStreamWaitEvent(lanes[k], ev->fork, 0) == hipSuccess;
+        if (!ok) {
+            ssn_set_error("conv wgrad pl group: fork of the side streams failed: %s", hipGetErrorString(hipGetLastError()));
+            return SSN_ERR_LAUNCH;
+        }
+    }
+#endif
+    for (size_t k = 0; k < launches.size(); ++k) {
+        const Launch& L = launches[k];
+        hipStream_t s = fan > 0 ? lanes[k % (size_t)fan] : stream;
+        if (fan == 0) {
+            grid[k] = write_table(L, index[k]);
+            SSN_CHECK_ARG(grid[k] < (1l << 31), "conv wgrad pl group: too many blocks");
+        }
+        launch_family(L, index[k], grid[k], s);
+        if (per_family) {
+            SSN_CHECK_LAUNCH("conv_wgrad_pl_group");
+            rc = reduce(std::vector<const WgGroupItem*>(L.items.begin(), L.items.end()), s);
+            if (rc != SSN_OK) break;      // (the lanes are joined below whatever happened on them)
+        }
+    }
+#if defined(__HIP__)
+    if (fan > 0 && join) {
+        bool ok = true;
+        for (int k = 0; k < fan; ++k) {
+            ok = hipEventRecord(ev->join[k], lanes[k]) == hipSuccess && ok;
+            ok = hipStreamWaitEvent(stream, ev->join[k], 0) == hipSuccess && ok;
+        }
+        if (!ok && rc == SSN_OK) {
+            ssn_set_error("conv wgrad pl group: join of the side streams failed: %s", hipGetErrorString(hipGetLastError()));
+            return SSN_ERR_LAUNCH;
+        }
+    }
+#endif
+    if (rc != SSN_OK) return rc;
+    SSN_CHECK_LAUNCH("conv_wgrad_pl_group");
+    if (per_family) return SSN_OK;
+    std::vector<const WgGroupItem*> all((size_t)count);
+    for (int i = 0; i < count; ++i) all[(size_t)i] = &items[(size_t)i];
+    return reduce(all, stream);
+}
+}  // namespace
+
+extern "C" int ssn_conv_wgrad_pl_group(int count, const void* const* g_hi, const void* const* g_lo, const void* const* x_hi,
+                                       const void* const* x_lo, float* const* dw, float* const* db, const int* shape,
+                                       const long* groups, const float* const* g_scale, const float* const* x_scale, void* workspace,
+                                       long ws_bytes, void* table, long table_bytes, hipStream_t stream) {
+    return wgrad_group_run(count, g_hi, g_lo, x_hi, x_lo, dw, db, shape, groups, g_scale, x_scale, workspace, ws_bytes, table,
+                           table_bytes, stream, false, nullptr, 0, true);
+}
+
+// ssn_conv_wgrad_pl_group with (a) each family's slabs summed right behind its kernel, the family with the most slab bytes first,
+// and (b) the families fanned out over `n_lanes` (<= 8) side streams of the caller: the table writes stay on `stream`, family k and
+// its reduction run on lanes[k % n_lanes], every lane waits for the table writes.  join != 0: `stream` waits for every lane before
+// the call returns; join == 0: the lanes are left running and the CALLER joins them to `stream` (a later call with join != 0 on the
+// same lanes does) -- the way to run a group beside the work that follows it on `stream` without a second level of forks.  The
+// events are created once per device, outside any capture; a first call on a capturing stream keeps to `stream`.  n_lanes == 0:
+// one stream.  Results are those of ssn_conv_wgrad_pl_group bit for bit: no problem's summation order depends on where it runs.
+extern "C" int ssn_conv_wgrad_pl_group_lanes(int count, const void* const* g_hi, const void* const* g_lo, const void* const* x_hi,
+                                             const void* const* x_lo, float* const* dw, float* const* db, const int* shape,
+                                             const long* groups, const float* const* g_scale, const float* const* x_scale,
+                                             void* workspace, long ws_bytes, void* table, long table_bytes, hipStream_t stream,
+                                             const hipStream_t* lanes, int n_lanes, int join) {
+    return wgrad_group_run(count, g_hi, g_lo, x_hi, x_lo, dw, db, shape, groups, g_scale, x_scale, workspace, ws_bytes, table,
+                           table_bytes, stream, true, lanes, n_lanes, join != 0);
 }
 
 // Weight + bias gradient on planes slices: g = dY [N, Cout, Ho, Wo] (final: its ReLU / BN backward applied), x = the layer's

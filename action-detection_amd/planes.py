@@ -257,19 +257,22 @@ class WgradJob:
     """One problem of a grouped weight-gradient launch: the arguments of ``conv_wgrad`` (g: final output gradient slice, x: the layer's
     input slice, dw / db: fp32 destinations) + an optional tile hint (-1: the library chooses)."""
 
-    __slots__ = ("g", "x", "dw", "db", "kh", "kw", "stride", "pad_h", "pad_w", "cin", "g_row_split", "g_row_gap", "hint")
+    __slots__ = ("g", "x", "dw", "db", "kh", "kw", "stride", "pad_h", "pad_w", "cin", "g_row_split", "g_row_gap", "hint", "units")
 
-    def __init__(self, g, x, dw, db, kh, kw, stride, pad_h, pad_w, cin=None, g_row_split=0, g_row_gap=0, hint=-1):
+    def __init__(self, g, x, dw, db, kh, kw, stride, pad_h, pad_w, cin=None, g_row_split=0, g_row_gap=0, hint=-1, units=0):
         self.g, self.x, self.dw, self.db = g, x, dw, db
         self.kh, self.kw, self.stride, self.pad_h, self.pad_w = int(kh), int(kw), int(stride), int(pad_h), int(pad_w)
         self.cin = x.c if cin is None else int(cin)
         self.g_row_split, self.g_row_gap, self.hint = int(g_row_split), int(g_row_gap), int(hint)
+        # units per split (0: planned by the call).  A call that holds PART of a pass's problems gives each the value of the whole
+        # pass's plan (``wgrad_group_plan``), so that its slabs are split -- and summed -- exactly as in one call.
+        self.units = int(units)
 
     def shape16(self):
         h, w = self.x.hw
         ho, wo = self.g.hw
         return [self.x.n, self.cin, h, w, self.g.c, ho, wo, self.kh, self.kw, self.stride, self.pad_h, self.pad_w,
-                self.g_row_split, self.g_row_gap, self.hint, 0]
+                self.g_row_split, self.g_row_gap, self.hint, self.units]
 
 
 def _wgrad_group_arrays(jobs):
@@ -295,9 +298,13 @@ def wgrad_group_plan(jobs):
     return ws, int(lib.cdll.ssn_conv_wgrad_pl_group_table_bytes(n)), [tuple(plan[4 * i:4 * i + 4]) for i in range(n)]
 
 
-def conv_wgrad_group(jobs, workspace=None, table=None):
+def conv_wgrad_group(jobs, workspace=None, table=None, streams=None, join=True):
     """Every weight + bias gradient of ``jobs`` (WgradJob) in at most five launches + one reduction (ssn_conv_wgrad_pl_group).
-    workspace (fp32 tensor) / table (uint8 tensor): buffers of at least ``wgrad_group_plan(jobs)`` bytes, allocated when None."""
+    workspace (fp32 tensor) / table (uint8 tensor): buffers of at least ``wgrad_group_plan(jobs)`` bytes, allocated when None.
+    streams: a sequence of torch streams (may be empty) -> ssn_conv_wgrad_pl_group_lanes: every family's slabs are reduced right
+    behind its kernel, the family with the largest slabs first, and family k runs on streams[k % len(streams)], forked behind the
+    table writes of the current stream.  join=False leaves the streams running: the caller joins them to the current stream (and
+    must keep workspace / table / operands untouched until then)."""
     import ctypes
     if not jobs:
         return
@@ -319,10 +326,16 @@ def conv_wgrad_group(jobs, workspace=None, table=None):
     dws = vp(*[_p(j.dw) for j in jobs])
     dbs = vp(*[_p(j.db) for j in jobs])
     gs, xs = vp(*[j.g.t.scale_ptr for j in jobs]), vp(*[j.x.t.scale_ptr for j in jobs])
-    lib.call("ssn_conv_wgrad_pl_group", n, ctypes.addressof(g_hi), ctypes.addressof(g_lo), ctypes.addressof(x_hi),
-             ctypes.addressof(x_lo), ctypes.addressof(dws), ctypes.addressof(dbs), ctypes.addressof(shape), ctypes.addressof(groups),
-             ctypes.addressof(gs), ctypes.addressof(xs), _p(workspace), workspace.numel() * workspace.element_size(), _p(table),
-             table.numel() * table.element_size(), _st(lib, first.t))
+    args = (n, ctypes.addressof(g_hi), ctypes.addressof(g_lo), ctypes.addressof(x_hi),
+            ctypes.addressof(x_lo), ctypes.addressof(dws), ctypes.addressof(dbs), ctypes.addressof(shape), ctypes.addressof(groups),
+            ctypes.addressof(gs), ctypes.addressof(xs), _p(workspace), workspace.numel() * workspace.element_size(), _p(table),
+            table.numel() * table.element_size(), _st(lib, first.t))
+    if streams is None:
+        lib.call("ssn_conv_wgrad_pl_group", *args)
+        return
+    lanes = (ctypes.c_void_p * len(streams))(*[s.cuda_stream for s in streams]) if len(streams) else None
+    lib.call("ssn_conv_wgrad_pl_group_lanes", *args, ctypes.addressof(lanes) if lanes is not None else None, len(streams),
+             int(bool(join)))
 
 
 def conv_dgrad_s2(dy, wt_packed, dx, pad, accumulate=False, tile_cfg=-1, mask=None, mask_scale=None):

@@ -598,13 +598,24 @@ def run_backward(net, dfeat, saved, hook=True):
                                 for q in plan if q["kind"] == "conv")
         pending_post = []                         # ... and what has to follow their reduction (the stem: space-to-depth taps -> 7x7)
 
+        # net.wgrad_lanes: every family's slab sum right behind its kernel, and the families on side streams of their own, forked
+        # from this stream and joined to it inside the call (ssn_conv_wgrad_pl_group_lanes) -- the five whole-GPU grids no longer
+        # drain one after the other, and the memory-bound sums run under the matrix-bound grids.  The streams are off with the
+        # other streams of the pass (one stream: bench.py --single-stream, the one-kernel-at-a-time profiling pass).
+        if not (net.wgrad_lanes and net.group_wgrad):
+            wl_streams = None
+        elif dfeat.is_cuda and net.overlap_wgrad and net.branch_lanes:
+            wl_streams = net._wgrad_streams(dev, 3)
+        else:
+            wl_streams = []
+
         def flush():
             if pending_wgrad:
-                # every weight gradient recorded since the last flush: <= 5 launches over a device-resident problem table + ONE
-                # reduction (ssn_conv_wgrad_pl_group) -- their output gradients are all final by now, and they depend on nothing else
+                # every weight gradient recorded since the last flush: <= 5 launches over a device-resident problem table + their
+                # reductions (ssn_conv_wgrad_pl_group) -- their output gradients are all final by now, and they depend on nothing else
                 jobs = [j for j, _ in pending_wgrad]
                 net._timed("conv_wgrad_pl", "group", sum(f for _, f in pending_wgrad),
-                           lambda: P.conv_wgrad_group(jobs, *net._wgrad_group_buffers(jobs, dev)))
+                           lambda: P.conv_wgrad_group(jobs, *net._wgrad_group_buffers(jobs, dev), streams=wl_streams))
             if pending_reduce:       # (timed with the weight-gradient family it belongs to: bench.py's roofline_detail)
                 entries = list(pending_reduce)
                 net._timed("conv_wgrad_pl", "reduce_multi", 0.0, lambda: P.wgrad_reduce_multi(entries))

@@ -783,6 +783,18 @@ int ssn_conv_wgrad_pl_group(int count, const void* const* g_hi, const void* cons
                             const void* const* x_lo, float* const* dw, float* const* db, const int* shape, const long* groups,
                             const float* const* g_scale, const float* const* x_scale, void* workspace, long ws_bytes, void* table,
                             long table_bytes, hipStream_t stream);
+/* shape[16 i + 15] > 0: units per split of problem i, given by the caller instead of planned -- a call that holds only PART of a
+ * pass's problems passes what the plan of the whole pass (plan_out) gave them, so that its slabs are split, and summed, as in one
+ * call.  The same call with (a) every family's slabs reduced right behind its kernel, the family with the most slab bytes first,
+ * and (b) the families fanned out over n_lanes (<= 8) side streams of the caller: the table writes stay on `stream`, family k and
+ * its reduction run on lanes[k % n_lanes], forked behind the table writes by an event (created once per device, no timing, never
+ * inside a capture: a first call on a capturing stream keeps to `stream`).  join != 0: `stream` waits for every lane before the
+ * call returns; join == 0: the lanes are left running and the CALLER joins them (a later call with join != 0 on the same lanes
+ * does).  n_lanes == 0: one stream.  Bit-identical to ssn_conv_wgrad_pl_group.  Capturable, no host sync. */
+int ssn_conv_wgrad_pl_group_lanes(int count, const void* const* g_hi, const void* const* g_lo, const void* const* x_hi,
+                                  const void* const* x_lo, float* const* dw, float* const* db, const int* shape, const long* groups,
+                                  const float* const* g_scale, const float* const* x_scale, void* workspace, long ws_bytes,
+                                  void* table, long table_bytes, hipStream_t stream, const hipStream_t* lanes, int n_lanes, int join);
 long ssn_conv_wgrad_pl_group_workspace_bytes(int count, const int* shape, const long* groups, int* plan_out);
 long ssn_conv_wgrad_pl_group_table_bytes(int count);
 void ssn_conv_wgrad_pl_group_tuning(double fixed_nine, double fixed_one, int min_units_nine, int min_units_one); /* tooling / tests: planner constants (<= 0: keep) */
