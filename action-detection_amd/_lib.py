@@ -19,7 +19,7 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(_HERE, "libssn_hip.so")
-SOURCES = ["conv_igemm.hip", "conv_x6.hip", "conv_x6_rect.hip", "conv_wgrad.hip", "conv_wgrad_x6.hip", "elementwise.hip", "bn_train.hip", "frames.hip", "detect.hip", "detect_batch.hip", "pool.hip", "stpp.hip", "heads_losses.hip", "conv_pl.hip", "planes_ops.hip", "planes_bn.hip", "wgrad_pl.hip", "tag.hip", "eval.hip", "actionness.hip", "train_step.hip", "flow.hip", "jpeg.hip", "jpeg_encode.hip", "jpeg_transcode.hip", "video_cls.hip", "proposal_list.hip", "proposal_eval.hip", "test_table.hip"]
+SOURCES = ["conv_igemm.hip", "conv_x6.hip", "conv_x6_rect.hip", "conv_wgrad.hip", "conv_wgrad_x6.hip", "elementwise.hip", "bn_train.hip", "frames.hip", "detect.hip", "detect_batch.hip", "pool.hip", "stpp.hip", "heads_losses.hip", "conv_pl.hip", "planes_ops.hip", "planes_bn.hip", "wgrad_pl.hip", "tag.hip", "eval.hip", "actionness.hip", "train_step.hip", "flow.hip", "jpeg.hip", "jpeg_encode.hip", "jpeg_transcode.hip", "video_cls.hip", "proposal_list.hip", "proposal_text.hip", "proposal_eval.hip", "test_table.hip"]
 
 STPP_MAX_PARTS = 24
 
@@ -84,6 +84,8 @@ _SIGS = {
     "ssn_sw_count": "pippipp",
     "ssn_sw_fill": "pippiipp",
     "ssn_proposal_list_rows": "ppippippipppp",
+    "ssn_proposal_text_size": "pppi" + "ppppp" + "ipip" + "lpp" + "iii" + "ppp",
+    "ssn_proposal_text_fill": "pppi" + "ppppp" + "ipip" + "plpp" + "iii" + "pplpp",
     "ssn_test_table_mark": "ppipippppp",
     "ssn_test_table_fill": "ppippippppippippppppp",
     "ssn_proposal_eval_rank": "ppiiplpplp",

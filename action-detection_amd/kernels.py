@@ -1165,6 +1165,79 @@ def proposal_list_rows(gt_span, gt_off, prop, prop_off, frame_cnt, durations):
     return gt_frames, frames, status
 
 
+_PROPOSAL_TEXT_BLOCK = 256
+
+
+class ProposalTextInputs(namedtuple("ProposalTextInputs", "gt_label gt_frames gt_off label iou overlap_self frames prop_off "
+                                    "frame_cnt paths path_off write item_off n_items first_index")):
+    """What ssn_proposal_text_size / _fill read (include/ssn_hip.h), ANY device arrays of these shapes: gt_label [G] int32 as
+    written, gt_frames [G, 2] int32, gt_off [V + 1] int32, label [P] int32, iou / overlap_self [P] fp64, frames [P, 2] int32,
+    prop_off [V + 1] int32, frame_cnt [V] int32, paths uint8 (the records' path bytes back to back), path_off [W + 1] int32,
+    write [W] int32 (the video of every record), item_off [W + 1] int32 (prefix sums of 3 + n_gt + K over the records),
+    n_items (their total, a host int), first_index."""
+
+    def check(self, who):
+        g, p, v, w = self.gt_label.numel(), self.label.numel(), self.frame_cnt.numel(), self.write.numel()
+        i32 = [(self.gt_label, (g,)), (self.gt_frames, (g, 2)), (self.gt_off, (v + 1,)), (self.label, (p,)), (self.frames, (p, 2)),
+               (self.prop_off, (v + 1,)), (self.frame_cnt, (v,)), (self.path_off, (w + 1,)), (self.write, (w,)),
+               (self.item_off, (w + 1,))]
+        if v < 1 or w < 1 or any(t.dtype != torch.int32 or tuple(t.shape) != s for t, s in i32):
+            raise ValueError("%s: the integer inputs must be int32 of the shapes of ProposalTextInputs, V >= 1 and W >= 1" % who)
+        if self.iou.dtype != torch.float64 or self.iou.shape != (p,) or self.overlap_self.dtype != torch.float64 \
+                or self.overlap_self.shape != (p,) or self.paths.dtype != torch.uint8 or self.paths.dim() != 1:
+            raise ValueError("%s: iou / overlap_self must be float64 [P] and paths uint8 [bytes]" % who)
+        n, first = int(self.n_items), int(self.first_index)
+        if n < 3 * w or n >= 2 ** 31 or first < 0 or first + w >= 2 ** 31 or self.paths.numel() >= 2 ** 30:
+            raise ValueError("%s: %d items for %d records, first index %d, %d path bytes" % (who, n, w, first, self.paths.numel()))
+        return g, p, v, w, n, first
+
+    def head(self, g, p, v):
+        """the arguments both entries begin with"""
+        return (_p(self.gt_label) if g else None, _p(self.gt_frames) if g else None, _p(self.gt_off), g,
+                _p(self.label) if p else None, _p(self.iou) if p else None, _p(self.overlap_self) if p else None,
+                _p(self.frames) if p else None, _p(self.prop_off), p, _p(self.frame_cnt), v)
+
+
+def proposal_text_items(gt_off, prop_off, write):
+    """item_off of ProposalTextInputs on the HOST: gt_off / prop_off [V + 1] and write [W], numpy -> int64 [W + 1]."""
+    import numpy as np
+    gt_off, prop_off, write = (np.asarray(x, dtype=np.int64) for x in (gt_off, prop_off, write))
+    per_record = 3 + (gt_off[1:] - gt_off[:-1])[write] + (prop_off[1:] - prop_off[:-1])[write]
+    return np.concatenate([[0], np.cumsum(per_record)]).astype(np.int64)
+
+
+def proposal_text_size(inp, status=None):
+    """ssn_proposal_text_size: -> (bp [ceil(n_items / 256) + 1] int32 whose last word is the byte count of the text, or -1
+    for 2^31 and more; status [V] int32 with bit 2 set for the videos that hold a float '%.4f' is not formed of on the
+    device).  status given: ORed into."""
+    lib = _check(*[t for t in inp if torch.is_tensor(t)])
+    g, p, v, w, n, first = inp.check("proposal_text_size")
+    dev = inp.write.device
+    if status is None:
+        status = torch.zeros(v, device=dev, dtype=torch.int32)
+    elif status.shape != (v,) or status.dtype != torch.int32 or not status.is_contiguous():
+        raise ValueError("proposal_text_size: status must be int32 [V]")
+    bp = torch.zeros((n + _PROPOSAL_TEXT_BLOCK - 1) // _PROPOSAL_TEXT_BLOCK + 1, device=dev, dtype=torch.int32)
+    lib.call("ssn_proposal_text_size", *(inp.head(g, p, v) + (_p(inp.path_off), inp.paths.numel(), _p(inp.write), _p(inp.item_off),
+                                                             w, n, first, _p(bp), _p(status), _stream(lib, inp.write))))
+    return bp, status
+
+
+def proposal_text_fill(inp, bp, out):
+    """ssn_proposal_text_fill: bp of proposal_text_size, out uint8 [bytes of the text or more] (a contiguous view at any
+    alignment; only the text's bytes are written) -> rec_off [W + 1] int32."""
+    lib = _check(bp, out, *[t for t in inp if torch.is_tensor(t)])
+    g, p, v, w, n, first = inp.check("proposal_text_fill")
+    if bp.dtype != torch.int32 or bp.shape != ((n + _PROPOSAL_TEXT_BLOCK - 1) // _PROPOSAL_TEXT_BLOCK + 1,) \
+            or out.dtype != torch.uint8 or out.dim() != 1 or out.numel() < 1 or out.numel() >= 2 ** 31:
+        raise ValueError("proposal_text_fill: bp must be what proposal_text_size returned and out uint8 [1 ... 2^31 - 1]")
+    rec_off = torch.zeros(w + 1, device=inp.write.device, dtype=torch.int32)
+    lib.call("ssn_proposal_text_fill", *(inp.head(g, p, v) + (_p(inp.paths) if inp.paths.numel() else None, _p(inp.path_off),
+                                                             inp.paths.numel(), _p(inp.write), _p(inp.item_off), w, n, first,
+                                                             _p(bp), _p(out), out.numel(), _p(rec_off), _stream(lib, inp.write))))
+    return rec_off
+
+
 # ------------------------------------------------------------------------------------ test table
 TEST_TABLE_MAX_PARTS = 16
 _TEST_TABLE_BLOCK = 256

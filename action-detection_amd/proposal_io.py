@@ -98,6 +98,13 @@ def write_proposal_file(filename, records):
             f.write(rec)
 
 
+def write_proposal_bytes(filename, data):
+    """A list file whose bytes are complete already, '# <index>' lines included
+    (``proposal_lists.ProposalListBuilder.build_text(...).data``): the file ``write_proposal_file`` writes from the same records."""
+    with open(filename, 'wb') as f:
+        f.write(data)
+
+
 def format_processed_record(idx, frame_path, frame_cnt, gt, prop):
     """One record of a processed list (gt: [label, start, end] ints; prop: [label, iou, overlap_self, start, end])."""
     text = "# {}\n{}\n{}\n1\n{}\n".format(idx, frame_path, frame_cnt, len(gt))

@@ -482,6 +482,35 @@ int ssn_proposal_list_rows(const double* gt_span, const int* gt_off, int G, cons
                            const int* frame_cnt, const double* durations, int V, int* gt_frames, int* frames, int* status,
                            hipStream_t stream);
 
+/* The text of the list file, formed on the device (csrc/proposal_text.hip): dump_window_list (ops/io.py:95-134) under the
+ * '# <index>' lines of the proposal scripts, byte for byte.  Inputs are the arrays the entries above left on the device:
+ * gt_label [G] int32 AS WRITTEN (label + 1), gt_frames [G][2], gt_off [V + 1]; label [P], iou / own [P] fp64, frames
+ * [P][2], prop_off [V + 1]; frame_cnt [V]; and the records to write: write [n_written] int32 (the video of record k),
+ * paths: the UTF-8 bytes of the records' paths back to back, path_off [n_written + 1] int32 into them (path_bytes in all,
+ * below 2^30), item_off [n_written + 1] int32: exclusive prefix sums of 3 + n_gt + K over the records (n_items in all).
+ * Record k is
+ *     # <first_index + k>\n<path>\n<frame_cnt>\n1\n<n_gt>\n   then   <label> <start> <end>\n   per ground-truth row,
+ *     <K>\n   then   <label> <iou:.4f> <own:.4f> <start> <end>\n   per proposal row; a record without proposals ends 0\n\n.
+ * Any int32 prints as C's %d; any finite double with |x| < 2^32 as C's %.4f (correctly rounded, ties to even, the sign
+ * of -0.0 kept; integer arithmetic).  NaN, +-inf and |x| >= 2^32 print as ?.???? and set bit 2 of the video's word in
+ * status [V] (ORed: the caller zeroes it or passes the status of ssn_proposal_list_rows).
+ *   size   bp [ceil(n_items / 256) + 1] int32: exclusive prefix sums of the bytes of every 256 items and, last, the bytes of
+ *          the text (-1: 2^31 or more).  ONE host read of that word sizes the output.
+ *   fill   out [out_bytes] uint8 (any alignment; nothing is written at or behind out_bytes), rec_off [n_written + 1] int32:
+ *          the first byte of every record and the end of the text.
+ * Three launches whatever V is; no atomic decides a position; rows, videos and path ranges the tables do not cover are
+ * left out.  All pointers device memory. */
+int ssn_proposal_text_size(const int* gt_label, const int* gt_frames, const int* gt_off, int G, const int* label,
+                           const double* iou, const double* own, const int* frames, const int* prop_off, int P,
+                           const int* frame_cnt, int V, const int* path_off, long path_bytes, const int* write,
+                           const int* item_off, int n_written, int n_items, int first_index, int* bp, int* status,
+                           hipStream_t stream);
+int ssn_proposal_text_fill(const int* gt_label, const int* gt_frames, const int* gt_off, int G, const int* label,
+                           const double* iou, const double* own, const int* frames, const int* prop_off, int P,
+                           const int* frame_cnt, int V, const unsigned char* paths, const int* path_off, long path_bytes,
+                           const int* write, const int* item_off, int n_written, int n_items, int first_index, const int* bp,
+                           unsigned char* out, long out_bytes, int* rec_off, hipStream_t stream);
+
 /* The test table of a batch of videos (csrc/test_table.hip): from the frame-number columns of a proposal list to what the
  * dense tester needs per proposal -- the rows ProposalSampler.test_ticks forms (ssn_dataset.py:393-428) and the row ranges
  * STPPReorgainzed computes from them (ops/ssn_ops.py:125-157), for all videos at once.  frames [P][2] int32 (start, end),

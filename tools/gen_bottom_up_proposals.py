@@ -38,6 +38,8 @@ def main(argv=None, db=None):
     ap.add_argument("--frame_path", type=str, default=None, help='folder of the frame folders (needed with --write_proposals)')
     ap.add_argument("--annotations", default=None, help="THUMOS14 annotation folder / ActivityNet JSON file")
     ap.add_argument("--device", type=str, default=None)
+    ap.add_argument("--device-text", action="store_true",
+                    help="with --write_proposals: form the bytes of the list file on the device too; the same file")
     ap.add_argument("--ar_an", type=float, nargs='?', const=0.0, default=None, metavar='N',
                     help='also print the AR-AN report (proposal_eval); N: the maximum average number of proposals per '
                          'video, without a value the mean')
@@ -49,7 +51,7 @@ def main(argv=None, db=None):
 
     import glob
     from action_detection_amd.datasets import open_database
-    from action_detection_amd.proposal_io import format_window_list_rows, write_proposal_file
+    from action_detection_amd.proposal_io import format_window_list_rows, write_proposal_bytes, write_proposal_file
     from action_detection_amd.proposal_lists import ProposalListBuilder
     from action_detection_amd.tag_proposals import TagProposalGenerator, merge_scores
 
@@ -91,7 +93,12 @@ def main(argv=None, db=None):
     builder = ProposalListBuilder(device=args.device)
     batch = builder.from_spans(videos, [r.seconds for r in tag])
     thresholds = np.arange(0.5, 1, 0.2)
-    result = builder.build(batch, frame_counts, recall_thresholds=thresholds)
+    device_text = bool(args.write_proposals) and args.device_text
+    if device_text:
+        result = builder.build_text(batch, frame_counts, [os.path.join(args.frame_path, n) for n in names],
+                                    recall_thresholds=thresholds)
+    else:
+        result = builder.build(batch, frame_counts, recall_thresholds=thresholds)
 
     print('{} groundtruth boxes from'.format(int(result.totals.sum())))
     print('average # of proposals: {}'.format(result.mean_proposals))
@@ -104,13 +111,16 @@ def main(argv=None, db=None):
         print(format_ar_an_report(result.ar_an))
 
     if args.write_proposals:
-        bad = [v.id for v, s in zip(videos, result.status) if s]
+        bad = [v.id for v, s in zip(videos, result.status) if s & 3]      # (bit 2, device text only: formatted on the host)
         if bad:
             raise ValueError("positions of {} are not finite or do not fit int32 (duration 0?)".format(", ".join(bad)))
-        records = [format_window_list_rows(os.path.join(args.frame_path, n), c, *result.rows(i))
-                   for i, (n, c) in enumerate(zip(names, frame_counts))]
-        write_proposal_file(args.write_proposals, records)
-        print('list written. got {} videos'.format(len(records)))
+        if device_text:
+            write_proposal_bytes(args.write_proposals, result.data)
+        else:
+            records = [format_window_list_rows(os.path.join(args.frame_path, n), c, *result.rows(i))
+                       for i, (n, c) in enumerate(zip(names, frame_counts))]
+            write_proposal_file(args.write_proposals, records)
+        print('list written. got {} videos'.format(len(videos)))
     return result
 
 
