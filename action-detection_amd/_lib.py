@@ -19,7 +19,7 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.path.join(_HERE, "libssn_hip.so")
-SOURCES = ["conv_igemm.hip", "conv_x6.hip", "conv_x6_rect.hip", "conv_wgrad.hip", "conv_wgrad_x6.hip", "elementwise.hip", "bn_train.hip", "frames.hip", "detect.hip", "detect_batch.hip", "pool.hip", "stpp.hip", "heads_losses.hip", "conv_pl.hip", "planes_ops.hip", "planes_bn.hip", "wgrad_pl.hip", "tag.hip", "eval.hip", "actionness.hip", "train_step.hip", "flow.hip", "jpeg.hip", "jpeg_encode.hip", "jpeg_transcode.hip", "video_cls.hip", "proposal_list.hip", "proposal_text.hip", "proposal_eval.hip", "test_table.hip"]
+SOURCES = ["conv_igemm.hip", "conv_x6.hip", "conv_x6_rect.hip", "conv_wgrad.hip", "conv_wgrad_x6.hip", "elementwise.hip", "bn_train.hip", "frames.hip", "detect.hip", "detect_batch.hip", "pool.hip", "stpp.hip", "heads_losses.hip", "conv_pl.hip", "planes_ops.hip", "planes_bn.hip", "wgrad_pl.hip", "tag.hip", "eval.hip", "actionness.hip", "train_step.hip", "flow.hip", "jpeg.hip", "jpeg_encode.hip", "jpeg_transcode.hip", "jpeg_roundtrip.hip", "video_cls.hip", "proposal_list.hip", "proposal_text.hip", "proposal_eval.hip", "test_table.hip"]
 
 STPP_MAX_PARTS = 24
 
@@ -120,6 +120,7 @@ _SIGS = {
     "ssn_jpeg_enc_assemble": "plpiplpplpplpppp",
     "ssn_jpeg_transcode_layout": "p",
     "ssn_jpeg_transcode_blocks": "plpiiplpp",
+    "ssn_jpeg_roundtrip_gray": "ppiiipp",
     "ssn_frames_crop_normalize": "ppiiiiiiipppiipipip",
     "ssn_frames_crop_resize_normalize": "ppiiiiiippiipipipup",
     "ssn_frames_scale": "ppiiiiiipup",
@@ -303,7 +304,7 @@ def build(force=False, verbose=False):
     a multi-GPU launch all call this)."""
     import fcntl
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
-    deps = srcs + [os.path.join(CSRC, h) for h in ("ssn_common.h", "conv_epilogue.h", "conv_x6_kernel.h", "planes.h", "conv_pl_epilogue.inc", "detect_common.h", "eval_common.h")]
+    deps = srcs + [os.path.join(CSRC, h) for h in ("ssn_common.h", "conv_epilogue.h", "conv_x6_kernel.h", "planes.h", "conv_pl_epilogue.inc", "detect_common.h", "eval_common.h", "jpeg_dct.h")]
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
     stamp_path = LIB_PATH + ".stamp"
     want = _source_stamp(deps, flags)

@@ -15,6 +15,7 @@
 // Nothing a file says is trusted past the parser: every bitstream read is bounded by the unit's byte range (bytes past its end
 // read as zero), every coefficient write by the image's block count AND the buffer's, every plane / pixel write by the buffer.
 #include "ssn_common.h"
+#include "jpeg_dct.h"      // jpeg_idct8
 
 namespace {
 
@@ -192,49 +193,6 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const unsigned char* b
         }
     }
     if (err) atomicOr(status + image, err);
-}
-
-// jidctint.c's jpeg_idct_islow, one dimension: CONST_BITS 13, results descaled by `shift` with rounding
-__device__ __forceinline__ void jpeg_idct8(int* x, int stride, int shift) {
-    int z2 = x[2 * stride], z3 = x[6 * stride];
-    int z1 = (z2 + z3) * 4433;
-    int tmp2 = z1 - z3 * 15137;
-    int tmp3 = z1 + z2 * 6270;
-    z2 = x[0];
-    z3 = x[4 * stride];
-    int tmp0 = (int)((unsigned)(z2 + z3) << 13);
-    int tmp1 = (int)((unsigned)(z2 - z3) << 13);
-    const int tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
-    tmp0 = x[7 * stride];
-    tmp1 = x[5 * stride];
-    tmp2 = x[3 * stride];
-    tmp3 = x[1 * stride];
-    z1 = tmp0 + tmp3;
-    z2 = tmp1 + tmp2;
-    z3 = tmp0 + tmp2;
-    int z4 = tmp1 + tmp3;
-    const int z5 = (z3 + z4) * 9633;
-    tmp0 *= 2446;
-    tmp1 *= 16819;
-    tmp2 *= 25172;
-    tmp3 *= 12299;
-    z1 *= -7373;
-    z2 *= -20995;
-    z3 = z3 * -16069 + z5;
-    z4 = z4 * -3196 + z5;
-    tmp0 += z1 + z3;
-    tmp1 += z2 + z4;
-    tmp2 += z2 + z3;
-    tmp3 += z1 + z4;
-    const int half = 1 << (shift - 1);
-    x[0] = (tmp10 + tmp3 + half) >> shift;
-    x[7 * stride] = (tmp10 - tmp3 + half) >> shift;
-    x[1 * stride] = (tmp11 + tmp2 + half) >> shift;
-    x[6 * stride] = (tmp11 - tmp2 + half) >> shift;
-    x[2 * stride] = (tmp12 + tmp1 + half) >> shift;
-    x[5 * stride] = (tmp12 - tmp1 + half) >> shift;
-    x[3 * stride] = (tmp13 + tmp0 + half) >> shift;
-    x[4 * stride] = (tmp13 - tmp0 + half) >> shift;
 }
 
 // bytes of an image's component planes (padded to whole MCUs), luma first

@@ -334,3 +334,36 @@ class JpegEncoder(object):
         files = batch.to_bytes()
         self.downloaded_bytes = sum(len(f) for f in files) + 8 * n
         return files
+
+
+_ROUNDTRIP_TABLES = {}      # (quality, device) -> int32 [64] on that device
+
+
+def roundtrip_gray(images, quality=95, out=None):
+    """The pixels of gray images after ``Image.fromarray(a).save(f, "JPEG", quality=quality)`` and ``Image.open(f).convert("L")``,
+    bit for bit, without the file and without the entropy coding in between (csrc/jpeg_roundtrip.hip): one launch.
+
+    images: uint8 [N, H, W] or [N, H, W, 1] on the device, contiguous or not (a non-contiguous tensor is copied first).  out: where to
+    write (same shape, contiguous; ``images`` itself for an in-place call).  -> uint8 of the shape of ``images``."""
+    from . import _lib
+    if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
+        raise ValueError("roundtrip_gray: quality is an integer 1 .. 100, got %r" % (quality,))
+    if not torch.is_tensor(images) or images.dtype != torch.uint8:
+        raise ValueError("roundtrip_gray: images are a uint8 tensor, got %s" % (images.dtype if torch.is_tensor(images) else type(images)))
+    if images.dim() not in (3, 4) or (images.dim() == 4 and images.shape[-1] != 1):
+        raise ValueError("roundtrip_gray: images are [N, H, W] or [N, H, W, 1], got %s" % (tuple(images.shape),))
+    if not images.is_cuda and not _lib.emulator_active():
+        raise ValueError("roundtrip_gray: images must be on the device (there is no CPU path)")
+    if min(images.shape) < 1 or images.shape[1] > 65535 or images.shape[2] > 65535:
+        raise ValueError("roundtrip_gray: N >= 1, H and W 1 .. 65535, got %s" % (tuple(images.shape),))
+    if out is not None and (not torch.is_tensor(out) or out.dtype != torch.uint8 or out.shape != images.shape or out.device != images.device
+                            or not out.is_contiguous()):
+        raise ValueError("roundtrip_gray: out must be a contiguous uint8 tensor of the shape and device of images")
+    shape = images.shape
+    src = images.reshape(shape[:3]).contiguous()
+    key = (quality, src.device)
+    table = _ROUNDTRIP_TABLES.get(key)
+    if table is None:
+        table = _ROUNDTRIP_TABLES[key] = torch.from_numpy(quant_tables(quality)[0].astype(np.int32)).to(src.device)
+    res = K.jpeg_roundtrip_gray(src, table, None if out is None else out.view(shape[:3]))
+    return res.view(shape)

@@ -2141,3 +2141,23 @@ def jpeg_transcode_blocks(src, desc, max_blocks, dst, status):
         raise ValueError("jpeg_transcode_blocks: max_blocks must be positive")
     lib.call("ssn_jpeg_transcode_blocks", _p(src), src.shape[0], _p(desc), desc.shape[0], int(max_blocks), _p(dst), dst.shape[0],
              _p(status), _stream(lib, dst))
+
+
+# ------------------------------------------------------------------------------------ gray JPEG round trip (csrc/jpeg_roundtrip.hip)
+def jpeg_roundtrip_gray(src, quant64, out=None):
+    """ssn_jpeg_roundtrip_gray: src uint8 [N, H, W]; quant64 int32 [64] on the device (natural order, 1 .. 255); out uint8 [N, H, W]
+    (written; may be src itself; allocated when None) -> out."""
+    if out is None:
+        out = torch.empty_like(src)
+    lib = _check(src, quant64, out)
+    if src.dtype != torch.uint8 or src.dim() != 3 or min(src.shape) < 1 or src.shape[1] > 65535 or src.shape[2] > 65535:
+        raise ValueError("jpeg_roundtrip_gray: src must be uint8 [N, H, W], N >= 1, H and W 1 .. 65535")
+    if out.dtype != torch.uint8 or out.shape != src.shape or out.device != src.device:
+        raise ValueError("jpeg_roundtrip_gray: out must be uint8 of src's shape on src's device")
+    if quant64.dtype != torch.int32 or tuple(quant64.shape) != (64,) or quant64.device != src.device:
+        raise ValueError("jpeg_roundtrip_gray: quant64 must be int32 [64] on src's device")
+    n, h, w = src.shape
+    if n >= 1 << 31:
+        raise ValueError("jpeg_roundtrip_gray: too many images")
+    lib.call("ssn_jpeg_roundtrip_gray", _p(src), _p(out), n, h, w, _p(quant64), _stream(lib, out))
+    return out

@@ -985,6 +985,14 @@ int ssn_jpeg_transcode_layout(int* desc_ints);
 int ssn_jpeg_transcode_blocks(const short* src, long src_blocks, const int* desc, int n_images, int max_blocks, short* dst,
                               long dst_blocks, int* status, hipStream_t stream);
 
+/* The pixels of a gray image after a round trip through a baseline JPEG file, without the file (csrc/jpeg_roundtrip.hip): bit for bit
+ * Image.open(f).convert("L") of what Image.fromarray(a).save(f, "JPEG", quality=) wrote.  src and dst uint8
+ * [n][h][w], contiguous; dst may be src.  quant64: DEVICE int32 [64], the luma table of the quality in natural order (1 .. 255), as
+ * jpeg_encode.quant_tables builds it.  Per 8 x 8 block: level shift, the encoder's forward DCT and quantisation, multiplication by
+ * the table, the decoder's inverse DCT and range limit; blocks over the right or bottom edge read the edge pixel repeated and store
+ * only what is inside the image. */
+int ssn_jpeg_roundtrip_gray(const unsigned char* src, unsigned char* dst, int n, int h, int w, const int* quant64, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

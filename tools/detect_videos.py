@@ -13,8 +13,11 @@ turns the scores into proposals, trained SSNs score the proposals, and the fused
 weights).  ``--proposals sliding`` replaces actionness + TAG by exponential sliding windows.  A video's frame count is the smallest
 count over the modalities in use; its duration is frames / ``--fps`` unless ``--durations`` (lines of ``video seconds``) gives it.
 NMS threshold, top-k and the softmax flag are those the data set is evaluated with (``tools/eval_detections.py --nms_threshold
---top_k --softmax_before_filter``).  Flow streams read the images ``tools/extract_flow.py`` wrote.  The networks are built by the
-code of ``tools/test_ssn.py`` and ``tools/extract_actionness.py``.  One process, one device.
+--top_k --softmax_before_filter``).  Flow streams read the images ``tools/extract_flow.py`` wrote, or with ``--flow on-the-fly``
+compute them from the RGB frames (``flow_stream.FlowStreamSource``: TV-L1, quantisation and the JPEG round trip of
+``--flow-quality`` on the device; the same numbers, no flow file).  The videos are then scored in consecutive groups whose flow
+fits ``--flow-cache-gb``, so that every Flow stream finds a group's flow in the cache and each pair is computed once.  The networks
+are built by the code of ``tools/test_ssn.py`` and ``tools/extract_actionness.py``.  One process, one device.
 """
 import argparse
 import json
@@ -60,7 +63,16 @@ def parse(argv=None):
     ap.add_argument("--flow_pref", type=str, default="")
     ap.add_argument("--save-scores", type=str, default=None, help="also write the score pickle tools/eval_detections.py reads")
     ap.add_argument("--device", type=str, default="cuda:0")
+    ap.add_argument("--flow", type=str, default="files", choices=["files", "on-the-fly"],
+                    help="Flow streams read the flow images of tools/extract_flow.py, or compute them from the RGB frames")
+    ap.add_argument("--flow-bound", type=float, default=20)
+    ap.add_argument("--flow-quality", type=int, default=95, help="JPEG quality of the flow images the networks were trained on")
+    ap.add_argument("--flow-iterations", type=int, default=300)
+    ap.add_argument("--flow-nscales", type=int, default=5)
+    ap.add_argument("--flow-warps", type=int, default=5)
+    ap.add_argument("--flow-cache-gb", type=float, default=16)
     args = ap.parse_args(argv)
+    args.flow_source = None      # the FlowStreamSource all Flow streams share (--flow on-the-fly; main() makes it)
     if args.proposals == "tag" and not args.actionness:
         ap.error("--proposals tag needs --actionness streams (or use --proposals sliding)")
     args.num_class = test_ssn.NUM_CLASS[args.dataset]
@@ -68,7 +80,7 @@ def parse(argv=None):
 
 
 def find_videos(args):
-    """-> [(video id, frame count, duration)] of the folders under FRAME_ROOT, alphabetical."""
+    """-> [(video id, frame count, duration)] of the folders under FRAME_ROOT, alphabetical.  ``args.rgb_frames``: their RGB frames."""
     from action_detection_amd.proposal_io import parse_directory
     frame_dict = parse_directory(args.frame_root, key_func=lambda x: x.split("/")[-1], flow_x_prefix=args.flow_pref + "x_",
                                  flow_y_prefix=args.flow_pref + "y_")
@@ -81,8 +93,11 @@ def find_videos(args):
                     vid, seconds = line.split()
                     durations[vid] = float(seconds)
     videos = []
+    args.rgb_frames = {vid: frame_dict[vid][1] for vid in frame_dict}
     for vid in sorted(frame_dict):
         _, rgb, flow = frame_dict[vid]
+        if args.flow == "on-the-fly":
+            flow = rgb - 1      # (pair i is computed from the frames i and i + 1: no flow file is needed)
         frames = min(([rgb] if "RGB" in modalities else []) + ([flow] if "Flow" in modalities else []))
         if frames < 1:
             raise ValueError("video {} has no frames of {}".format(vid, sorted(modalities)))
@@ -90,6 +105,93 @@ def find_videos(args):
     if not videos:
         raise ValueError("no video folder under {}".format(args.frame_root))
     return videos
+
+
+def flow_reader(args):
+    """The reader of a Flow stream: the shared on-the-fly source, or the flow files (decoded; with --gpu-decode their bytes)."""
+    from action_detection_amd import train_data as D
+    if args.flow_source is not None:
+        return args.flow_source
+    cls = D.CompressedFrameDirReader if args.gpu_decode else D.FrameDirReader
+    return cls(args.frame_root, "Flow", args.flow_pref)
+
+
+def device_chain_from_frames(chain):
+    """The transform behind the on-the-fly source with --gpu-decode: a DeviceTestChain fed with frames that are on the device."""
+    import functools
+    from action_detection_amd.flow_stream import chain_from_frames
+    return functools.partial(chain_from_frames, chain)
+
+
+def make_flow_source(args):
+    """--flow on-the-fly: the one FlowStreamSource of the run; a device tensor per request with --gpu-decode, else a host array in
+    front of the host chain."""
+    from action_detection_amd import train_data as D
+    from action_detection_amd.flow_stream import FlowStreamSource
+    from action_detection_amd.optical_flow import TVL1, FlowExtractor
+    cls = D.CompressedFrameDirReader if args.gpu_decode else D.FrameDirReader
+    extractor = FlowExtractor(TVL1(nscales=args.flow_nscales, warps=args.flow_warps, iterations=args.flow_iterations),
+                              bound=args.flow_bound)
+    return FlowStreamSource(cls(args.frame_root, "RGB"), args.rgb_frames, extractor, quality=args.flow_quality,
+                            cache_bytes=int(args.flow_cache_gb * (1 << 30)), output="device" if args.gpu_decode else "host",
+                            device=args.device)
+
+
+def flow_groups(args, videos):
+    """Consecutive groups of `videos` whose flow (``FlowStreamSource.flow_bytes``: 2 H W (T - 1) bytes a video, the size from the
+    first frame the RGB reader delivers) fits the cache budget together; a video past the budget is a group of its own
+    -> [[index into videos]]."""
+    budget = int(args.flow_cache_gb * (1 << 30))
+    groups, used = [], 0
+    for i, (vid, _, _) in enumerate(videos):
+        need = args.flow_source.flow_bytes(vid)
+        if groups and used + need <= budget:
+            groups[-1].append(i)
+            used += need
+        else:
+            groups.append([i])
+            used = need
+    return groups
+
+
+def ssn_flow_pairs(new_length, interval, frames, tick_batch=32):
+    """The pairs (0-based) a Flow stream of `new_length` frames a tick, a tick every `interval` frames, reads of a video of `frames`
+    flow frames: the frame numbers the detector's own generator asks a reader for (its tick rule through ``test_frame_batches``)."""
+    from action_detection_amd.detect import _TickRule, _Video
+    from action_detection_amd.test_data import test_frame_batches
+    asked = set()
+
+    def record(vid, numbers):
+        asked.update(int(f) - 1 for f in numbers)
+    for _ in test_frame_batches(_TickRule(new_length, interval), _Video("", int(frames), 0.0), record, lambda none: none, tick_batch):
+        pass
+    return sorted(asked)
+
+
+class GroupedResults(object):
+    """The DetectionResults of consecutive groups of videos as one: what the command writes and reports."""
+
+    def __init__(self, results):
+        self.results = list(results)
+        self.videos = [v for r in self.results for v in r.videos]
+        self.rows = sum(len(r.detections.rows) for r in self.results)
+
+    def to_activitynet(self, class_names):
+        out = self.results[0].to_activitynet(class_names)
+        for r in self.results[1:]:
+            out["results"].update(r.to_activitynet(class_names)["results"])      # (disjoint by video id)
+        return out
+
+    def host_scores(self):
+        scores = {}
+        for r in self.results:
+            scores.update(r.host_scores())
+        return scores
+
+    def save_scores(self, path):
+        import pickle
+        with open(path, "wb") as f:
+            pickle.dump(self.host_scores(), f, pickle.HIGHEST_PROTOCOL)
 
 
 def make_ssn_stream(args, modality, weights, weight):
@@ -104,6 +206,8 @@ def make_ssn_stream(args, modality, weights, weight):
                             proposal_list=os.devnull)
     built = test_ssn.SSNVideoTester(ns, args.device)
     tester, reader, transform = built.tester, built.reader, built.transform
+    if modality == "Flow" and args.flow_source is not None:
+        reader, transform = flow_reader(args), (device_chain_from_frames(transform) if args.gpu_decode else transform)
     return Stream(tester, reader, transform, 1 if modality == "RGB" else 5, weight)
 
 
@@ -118,18 +222,23 @@ def make_actionness_stream(args, modality, weights, weight):
     if args.gpu_decode:
         if args.test_crops != 10:
             raise ValueError("--gpu-decode scores the actionness streams with 10 crops, got --test_crops {}".format(args.test_crops))
-        reader = D.CompressedFrameDirReader(args.frame_root, modality, args.flow_pref)
-        transform = EA.device_transform(net, modality, args.device, scale=True)
+        if modality == "Flow" and args.flow_source is not None:
+            reader = flow_reader(args)
+            transform = device_chain_from_frames(TD.DeviceTestChain(net.input_size, net.scale_size, net.input_mean, net.input_std,
+                                                                    modality, args.test_crops, args.device))
+        else:
+            reader = D.CompressedFrameDirReader(args.frame_root, modality, args.flow_pref)
+            transform = EA.device_transform(net, modality, args.device, scale=True)
     else:
         # binary_test.py's host chain: ten crops are GroupOverSample as in the SSN tester's chain (the same transforms); one crop is
         # taken as that chain takes it, GroupScale + GroupCenterCrop (the backbone here takes square inputs only)
-        reader = D.FrameDirReader(args.frame_root, modality, args.flow_pref)
+        reader = flow_reader(args) if modality == "Flow" else D.FrameDirReader(args.frame_root, modality, args.flow_pref)
         transform = TD.host_test_chain(net.input_size, net.scale_size, net.input_mean, net.input_std, args.test_crops)
     return Stream(ActionnessTester(net, tick_batch=args.tick_batch), reader, transform,
                   1 if modality == "RGB" else 5, weight)
 
 
-def main(argv=None, make_ssn=make_ssn_stream, make_actionness=make_actionness_stream):
+def main(argv=None, make_ssn=make_ssn_stream, make_actionness=make_actionness_stream, make_flow=make_flow_source):
     args = parse(argv)
     import test_ssn
     from action_detection_amd.detect import ActionDetector
@@ -144,6 +253,10 @@ def main(argv=None, make_ssn=make_ssn_stream, make_actionness=make_actionness_st
             torch.cuda.set_device(torch.device(args.device))
     videos = find_videos(args)
     print("{} videos under {}".format(len(videos), args.frame_root))
+    modalities = {m for m, _, _ in list(args.ssn) + list(args.actionness)}
+    on_the_fly = args.flow == "on-the-fly" and "Flow" in modalities
+    if on_the_fly:
+        args.flow_source = make_flow(args)
     ssn = [make_ssn(args, *s) for s in args.ssn]
     sliding = args.proposals == "sliding"
     actionness = [] if sliding else [make_actionness(args, *s) for s in args.actionness]
@@ -153,7 +266,24 @@ def main(argv=None, make_ssn=make_ssn_stream, make_actionness=make_actionness_st
                               test_crops=args.test_crops, tick_batch=args.tick_batch, stpp_cfg=test_ssn.STPP[args.dataset],
                               device=args.device)
     proposals = [np.asarray(sliding_window_proposals(v[2]), dtype=np.float64).reshape(-1, 2) for v in videos] if sliding else None
-    result = detector.detect(videos, proposals=proposals)
+    if on_the_fly:
+        # the detector scores stream-major: a group's flow has to stay in the cache from the first Flow stream to the last
+        groups = flow_groups(args, videos)
+        # only SSN streams read the flow: they skip the pairs between two ticks' stacks, which are then not computed
+        flow_ssn = [st for st in detector.ssn if st.reader is args.flow_source]
+        prepare_only = bool(flow_ssn) and not any(st.reader is args.flow_source for st in detector.actionness)
+        results = []
+        for g in groups:
+            if prepare_only:
+                for i in g:
+                    pairs = set()
+                    for new_length in sorted({st.new_length for st in flow_ssn}):
+                        pairs.update(ssn_flow_pairs(new_length, args.frame_interval, videos[i][1], args.tick_batch))
+                    args.flow_source.prepare(videos[i][0], sorted(pairs))
+            results.append(detector.detect([videos[i] for i in g], proposals=None if proposals is None else [proposals[i] for i in g]))
+        result = results[0] if len(results) == 1 else GroupedResults(results)
+    else:
+        result = detector.detect(videos, proposals=proposals)
     if args.class_names:
         with open(args.class_names) as f:
             names = [line.strip() for line in f if line.strip()]
@@ -164,7 +294,13 @@ def main(argv=None, make_ssn=make_ssn_stream, make_actionness=make_actionness_st
         json.dump(out, f)
     if args.save_scores:
         result.save_scores(args.save_scores)
-    print("{} detections of {} videos written to {}".format(len(result.detections.rows), len(videos), args.out_json))
+    rows = result.rows if isinstance(result, GroupedResults) else len(result.detections.rows)
+    print("{} detections of {} videos written to {}".format(rows, len(videos), args.out_json))
+    if on_the_fly:
+        src = args.flow_source
+        print("flow on the fly: {} groups of videos; {} videos and {} pairs computed, {} requests from the cache".format(
+            len(groups), src.videos_computed, src.pairs_computed, src.cache_hits))
+        result.flow_groups, result.flow_source = groups, src
     return result
 
 
