@@ -176,6 +176,8 @@ _SIGS = {
     "ssn_pl_channel_sum_multi": "ippppipppplp",
     "ssn_conv_x6_pack_batch_begin": "",
     "ssn_conv_x6_pack_batch_end": "plip",
+    "ssn_conv_x6_pack_batch_end_lanes": "pliipp",
+    "ssn_conv_x6_pack_batch_join": "p",
     "ssn_pl_bn_train_stats": "pplpppppp" + "iiiffplp",
     "ssn_pl_bn_train_apply": "pplppplpp" + "ppppiiiip",
     "ssn_pl_bn_train_bwd": "pplpplpplp" + "ppppp" + "pplpp" + "pliiiplp",

@@ -217,6 +217,12 @@ class BNInception(nn.Module):
         self.pooled_mask = os.environ.get("SSN_POOLED_MASK", "1") != "0"   # planes_exec: stem pools' backward reads the pooled sign
         # planes_exec: all weight operands of a pass packed in three launches through a device-resident plan (kernels.PackBatch)
         self.batch_packing = os.environ.get("SSN_BATCH_PACKING", "1") != "0"
+        # planes_exec: only the stem's operand is packed on the pass's stream; every other layer's (forward and data-gradient images)
+        # on the side stream beside the stem convolution and its pool, joined in front of the first launch behind them
+        # (ssn_conv_x6_pack_batch_end_lanes / _join).  Same bytes.  OFF by default: measured beside the coalesced packing kernels it
+        # gains 0.01 ms per step, inside the run-to-run spread (profiles/pack_lanes_measured.txt); SSN_PACK_LANES=1 switches it on.
+        # It stays on one stream whenever branch_lanes is cleared (bench.py --single-stream, the eager per-launch profiling pass).
+        self.pack_lanes = os.environ.get("SSN_PACK_LANES", "0") != "0"
         # planes_exec: training-mode BatchNorm layers (bn_mode 'partial' / 'full') on the planes kernels of csrc/planes_bn.hip;
         # 0: plans with such layers run on the fp32-layout executor below (csrc/bn_train.hip)
         self.planes_train_bn = os.environ.get("SSN_PLANES_TRAIN_BN", "1") != "0"

@@ -32,6 +32,8 @@
 //  * Epilogue: per-channel vectors via LDS, branch-free buffer addressing (out-of-range rows/pixels fall off the
 //    buffer), read-modify-write operands fetched one accumulator tile ahead.
 #include "conv_x6_kernel.h"
+#include <map>
+#include <mutex>
 #include <unordered_map>
 #include <vector>
 
@@ -154,6 +156,135 @@ __device__ __forceinline__ void pack_entry_rows(const X6PackEntry& e, int lb) {
     }
 }
 
+// ---- the bodies of the device-resident plan: the same bytes, moved in 16-byte pieces ----
+// The element-wise bodies above read one float per lane at a stride of srckk (forward modes) or Cin * srckk (transposed modes)
+// floats and write two scattered dwords per lane.  Here a block stages a sub-tensor of the source -- 16 channels x a run of
+// XP rows x all source taps of one entry -- through LDS: the source is contiguous along the taps and then along the channels
+// (forward modes: one segment of 16 * srckk floats per row) or the rows (transposed modes: one segment of run * srckk floats
+// per channel), and is read with 16-byte loads wherever an aligned quad lies inside its segment; a lane then splits eight
+// channels of one (tap, row) and writes the two 16-byte chunks they make.  Entry, slab, row run and segment are decoded once
+// per block; the split itself (f16_split2_pair, the scale from the entry's tail) and the chunk swizzle are unchanged.
+constexpr int XP_LDS = 8192;     // floats a packing block stages: 16 channels x xp_run(srckk) rows x srckk taps at most
+constexpr int XP_SRCKK_MAX = 32; // (xp_run(32) = 16 rows)
+__host__ __device__ inline int xp_run(int srckk) {
+    const int r = (XP_LDS / 16 / srckk) & ~7;
+    return r > 128 ? 128 : r;
+}
+// blocks of one entry in the plan's packing launch
+inline int xp_plan_blocks(int cout, int cin, int mode, int srckk) {
+    const int M = mode ? cin : cout, C = mode ? cout : cin, R = xp_run(srckk);
+    return ((C + 15) / 16) * ((M + R - 1) / R);
+}
+__device__ __forceinline__ void pack_entry_amax_wide(const X6PackEntry& e, int lb) {
+    const long per = (long)e.cin * e.srckk;
+    const long n[4] = {(long)e.split * per, (long)(e.split2 - e.split) * per, (long)(e.split3 - e.split2) * per,
+                       (long)(e.cout - e.split3) * per};
+    const long base = (long)lb * XP_ACHUNK, end = base + XP_ACHUNK;
+    const int tid = (int)threadIdx.x;
+    float m = 0.f;
+    long s0 = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        // the part of source k inside this block's chunk: [a, b) of its elements (block-uniform)
+        const long a = (base > s0 ? base : s0) - s0, b = (end < s0 + n[k] ? end : s0 + n[k]) - s0;
+        s0 += n[k];
+        if (b <= a) continue;
+        const float* q = e.w[k] + a;
+        const int cnt = (int)(b - a);
+        int head = (4 - (int)((reinterpret_cast<uintptr_t>(q) >> 2) & 3)) & 3;     // floats in front of the first aligned quad
+        if (head > cnt) head = cnt;
+        const int nq = (cnt - head) >> 2, rest = cnt - head - 4 * nq;
+        for (int j = tid; j < nq; j += 256) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(q + head + 4 * j);
+            m = fmaxf(fmaxf(m, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+        }
+        if (tid < head) m = fmaxf(m, fabsf(q[tid]));
+        if (tid >= 64 && tid < 64 + rest) m = fmaxf(m, fabsf(q[head + 4 * nq + tid - 64]));
+    }
+    amax_emit_block(reinterpret_cast<float*>(e.out + e.rows_dw), m);
+}
+__device__ __forceinline__ void pack_entry_rows_staged(const X6PackEntry& e, int lb, float* lds) {
+    const int mode = e.mode, Cin = e.cin, KK = e.kk, SK = e.srckk;
+    const int M = mode ? Cin : e.cout, C = mode ? e.cout : Cin;
+    const int ngroups = (C + 15) / 16;
+    const int R = xp_run(SK), nrb = (M + R - 1) / R;
+    // neighbouring blocks read neighbouring memory: the channel group runs fastest in the forward modes, the row run in the others
+    int g, rb;
+    if (mode) {
+        g = lb / nrb;
+        rb = lb - g * nrb;
+    } else {
+        rb = lb / ngroups;
+        g = lb - rb * ngroups;
+    }
+    const int m0 = rb * R;
+    const int Rr = M - m0 < R ? M - m0 : R;                      // rows of this block
+    const int nC = C - 16 * g < 16 ? C - 16 * g : 16;            // channels of this block (rows above them are zero-filled)
+    const int nseg = mode ? nC : Rr;                             // contiguous source segments ...
+    const int L = (mode ? Rr : nC) * SK;                         // ... of L floats each, segment s at lds + s * L
+    const int nq = L / 4 + 2;                                    // aligned quads a segment can touch
+    const int tid = (int)threadIdx.x;
+    for (int i = tid; i < nseg * nq; i += 256) {
+        const int s = i / nq, j = i - s * nq;
+        const int co = mode ? 16 * g + s : m0 + s;
+        const float* src = co < e.split ? e.w[0] : (co < e.split2 ? e.w[1] : (co < e.split3 ? e.w[2] : e.w[3]));
+        const int cor = co < e.split ? co : (co < e.split2 ? co - e.split : (co < e.split3 ? co - e.split2 : co - e.split3));
+        const float* p = src + ((long)cor * Cin + (mode ? m0 : 16 * g)) * SK;
+        const int e0 = 4 * j - (int)((reinterpret_cast<uintptr_t>(p) >> 2) & 3);   // first element of quad j, from the segment's start
+        float* dst = lds + s * L;
+        if (e0 >= 0 && e0 + 4 <= L) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(p + e0);
+            dst[e0] = v[0];
+            dst[e0 + 1] = v[1];
+            dst[e0 + 2] = v[2];
+            dst[e0 + 3] = v[3];
+        } else {
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+                if (e0 + t >= 0 && e0 + t < L) dst[e0 + t] = p[e0 + t];
+        }
+    }
+    __syncthreads();
+    const float sa = f16_scale_of(__builtin_bit_cast(float, e.out[e.rows_dw]));
+    const bool wide = (reinterpret_cast<uintptr_t>(e.out) & 15) == 0;
+    const int cstep = mode ? L : SK, rstep = mode ? SK : L;
+    for (int i = tid; i < KK * Rr * 2; i += 256) {
+        const int khalf = i & 1, tr = i >> 1;
+        const int tap = tr / Rr, r = tr - tap * Rr;
+        const int stap = SK == KK ? (mode == 2 ? KK - 1 - tap : tap) : (int)((e.tapmap >> (4 * tap)) & 15u);
+        const float* at = lds + r * rstep + stap;
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int c = 8 * khalf + j;
+            v[j] = c < nC ? at[c * cstep] : 0.f;
+        }
+        u32x4 hi, lo;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            uint32_t h, l;
+            f16_split2_pair(v[2 * w], v[2 * w + 1], sa, h, l);
+            hi[w] = h;
+            lo[w] = l;
+        }
+        const int m = m0 + r;
+        uint32_t* row = e.out + ((long)(g * KK + tap) * M + m) * APITCH;
+        const int swz = (m >> 2) & 3;
+        uint32_t* ph = row + ((0 + khalf) ^ swz) * 4;
+        uint32_t* pl = row + ((2 + khalf) ^ swz) * 4;
+        if (wide) {
+            *reinterpret_cast<u32x4*>(ph) = hi;
+            *reinterpret_cast<u32x4*>(pl) = lo;
+        } else {
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                ph[w] = hi[w];
+                pl[w] = lo[w];
+            }
+        }
+    }
+}
+
 __global__ __launch_bounds__(64) void pack_x6_clear_tail_kernel(X6PackTable t) {
     for (int i = threadIdx.x; i < t.count * ATAIL; i += 64) t.out[i / ATAIL][t.rows_dw[i / ATAIL] + i % ATAIL] = 0u;
 }
@@ -195,13 +326,17 @@ __global__ __launch_bounds__(256) void pack_x6_plan_clear_kernel(const X6PackEnt
     for (int i = blockIdx.x * 256 + threadIdx.x; i < count * ATAIL; i += gridDim.x * 256)
         plan[i / ATAIL].out[plan[i / ATAIL].rows_dw + i % ATAIL] = 0u;
 }
-__global__ __launch_bounds__(256) void pack_x6_plan_amax_kernel(const X6PackEntry* plan, int count) {
-    const X6PackEntry e = plan[plan_entry_of_block(plan, count, (int)blockIdx.x, true)];
-    pack_entry_amax(e, (int)blockIdx.x - e.ablk0);
+// (plan, count: a run of the plan's entries; blk_base: the first block of that run in the numbering of the whole plan)
+__global__ __launch_bounds__(256) void pack_x6_plan_amax_kernel(const X6PackEntry* plan, int count, int blk_base) {
+    const int b = (int)blockIdx.x + blk_base;
+    const X6PackEntry e = plan[plan_entry_of_block(plan, count, b, true)];
+    pack_entry_amax_wide(e, b - e.ablk0);
 }
-__global__ __launch_bounds__(256) void pack_x6_plan_kernel(const X6PackEntry* plan, int count) {
-    const X6PackEntry e = plan[plan_entry_of_block(plan, count, (int)blockIdx.x, false)];
-    pack_entry_rows(e, (int)blockIdx.x - e.blk0);
+__global__ __launch_bounds__(256) void pack_x6_plan_kernel(const X6PackEntry* plan, int count, int blk_base) {
+    __shared__ float stage[XP_LDS];
+    const int b = (int)blockIdx.x + blk_base;
+    const X6PackEntry e = plan[plan_entry_of_block(plan, count, b, false)];
+    pack_entry_rows_staged(e, b - e.blk0, stage);
 }
 
 bool g_pack_batching = false;
@@ -414,7 +549,49 @@ extern "C" void ssn_conv_x6_pack_batch_abort(void) {
     g_pack_batching = false;
     g_pack_batch.clear();
 }
-extern "C" int ssn_conv_x6_pack_batch_end(void* plan, long plan_bytes, int force_write, hipStream_t stream) {
+namespace {
+#if defined(__HIP__)
+// Fork / join events of a packing pass split over two streams: created once per device (no timing), outside any capture, and
+// reused by every call.  `pending`: the side stream's join event has been recorded and nobody has waited for it yet.
+struct PackLaneEvents {
+    hipEvent_t fork, join;
+    bool pending;
+};
+std::mutex g_pack_lane_mu;
+std::map<int, PackLaneEvents> g_pack_lane_events;
+// (stream: nullptr = look up only, never create)
+PackLaneEvents* pack_lane_events(const hipStream_t* stream) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+    auto it = g_pack_lane_events.find(dev);
+    if (it != g_pack_lane_events.end()) return &it->second;
+    if (!stream) return nullptr;
+    hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(*stream, &status) != hipSuccess || status != hipStreamCaptureStatusNone) {
+        (void)hipGetLastError();
+        return nullptr;      // (no events yet and the stream is capturing: this call keeps to one stream)
+    }
+    PackLaneEvents ev;
+    ev.pending = false;
+    if (hipEventCreateWithFlags(&ev.fork, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&ev.join, hipEventDisableTiming) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    return &g_pack_lane_events.emplace(dev, ev).first->second;
+}
+#endif
+
+// clear / amax / pack of the plan's entries [first, first + n), whose blocks start at bb / ab in the numbering of the whole plan
+void launch_plan_run(const X6PackEntry* dev, int first, int n, int bb, int blocks, int ab, int ablocks, hipStream_t stream) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(pack_x6_plan_clear_kernel, dim3((unsigned)((n * ATAIL + 255) / 256)), dim3(256), 0, stream, dev + first, n);
+    if (ablocks > 0)
+        hipLaunchKernelGGL(pack_x6_plan_amax_kernel, dim3((unsigned)ablocks), dim3(256), 0, stream, dev + first, n, ab);
+    if (blocks > 0) hipLaunchKernelGGL(pack_x6_plan_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, dev + first, n, bb);
+}
+
+int pack_batch_run(void* plan, long plan_bytes, int force_write, int n_first, hipStream_t stream, hipStream_t side_stream) {
     SSN_CHECK_ARG(g_pack_batching, "conv x6 pack batch: not open");
     g_pack_batching = false;
     const int count = ssn_conv_x6_pack_batch_entries();
@@ -423,6 +600,44 @@ extern "C" int ssn_conv_x6_pack_batch_end(void* plan, long plan_bytes, int force
         g_pack_batch.clear();
         ssn_set_error("conv x6 pack batch: plan buffer %ld < %ld bytes", plan_bytes, (long)count * (long)sizeof(X6PackEntry));
         return SSN_ERR_WORKSPACE;
+    }
+    if (n_first < 0) n_first = count;      // (ssn_conv_x6_pack_batch_end)
+    if (n_first > count) {
+        g_pack_batch.clear();
+        ssn_set_error("conv x6 pack batch: %d leading entries of %d", n_first, count);
+        return SSN_ERR_ARG;
+    }
+    // the plan's packing launch has its own blocks (pack_entry_rows_staged): renumber the recorded tables, and find where the
+    // leading entries end in both launches
+    int split_bb = 0, split_ab = 0, seen = 0;
+    for (X6PackTable& t : g_pack_batch) {
+        int nb = 0;
+        for (int i = 0; i < t.count; ++i) {
+            if (t.srckk[i] < 1 || t.srckk[i] > XP_SRCKK_MAX) {
+                g_pack_batch.clear();
+                ssn_set_error("conv x6 pack batch: %d source taps (at most %d)", t.srckk[i], XP_SRCKK_MAX);
+                return SSN_ERR_ARG;
+            }
+            t.blk0[i] = nb;
+            nb += xp_plan_blocks(t.cout[i], t.cin[i], t.mode[i], t.srckk[i]);
+        }
+        t.blk0[t.count] = nb;
+    }
+    {
+        int bb = 0, ab = 0;
+        for (const X6PackTable& t : g_pack_batch) {
+            for (int i = 0; i < t.count; ++i, ++seen)
+                if (seen == n_first) {
+                    split_bb = bb + t.blk0[i];
+                    split_ab = ab + t.ablk0[i];
+                }
+            bb += t.blk0[t.count];
+            ab += t.ablk0[t.count];
+        }
+        if (n_first == count) {
+            split_bb = bb;
+            split_ab = ab;
+        }
     }
     uint64_t h = 1469598103934665603ull;      // FNV-1a over the recorded tables
     for (const X6PackTable& t : g_pack_batch) {
@@ -455,11 +670,73 @@ extern "C" int ssn_conv_x6_pack_batch_end(void* plan, long plan_bytes, int force
         g_plan_hash[plan] = h;
     }
     g_pack_batch.clear();
-    hipLaunchKernelGGL(pack_x6_plan_clear_kernel, dim3((unsigned)((count * ATAIL + 255) / 256)), dim3(256), 0, stream,
-                       (const X6PackEntry*)dev, count);
-    hipLaunchKernelGGL(pack_x6_plan_amax_kernel, dim3((unsigned)ablocks), dim3(256), 0, stream, (const X6PackEntry*)dev, count);
-    hipLaunchKernelGGL(pack_x6_plan_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, (const X6PackEntry*)dev, count);
-    SSN_CHECK_LAUNCH("conv_x6_pack_batch_end");
+    if (n_first == count || !side_stream) {
+        launch_plan_run(dev, 0, count, 0, blocks, 0, ablocks, stream);
+        SSN_CHECK_LAUNCH("conv_x6_pack_batch_end");
+        return SSN_OK;
+    }
+    // the leading entries on `stream`, the others on the side stream behind a fork event that sits behind the plan writes -- and
+    // with them behind everything the caller issued on `stream` before: the previous step's optimizer, the last reader of the images
+    hipStream_t rest = stream;
+#if defined(__HIP__)
+    std::lock_guard<std::mutex> lock(g_pack_lane_mu);
+    PackLaneEvents* ev = side_stream != stream ? pack_lane_events(&stream) : nullptr;
+    if (ev) {
+        if (hipEventRecord(ev->fork, stream) != hipSuccess || hipStreamWaitEvent(side_stream, ev->fork, 0) != hipSuccess) {
+            ssn_set_error("conv x6 pack batch: fork of the side stream failed: %s", hipGetErrorString(hipGetLastError()));
+            return SSN_ERR_LAUNCH;
+        }
+        rest = side_stream;
+    }
+#endif
+    launch_plan_run(dev, 0, n_first, 0, split_bb, 0, split_ab, stream);
+    launch_plan_run(dev, n_first, count - n_first, split_bb, blocks - split_bb, split_ab, ablocks - split_ab, rest);
+    SSN_CHECK_LAUNCH("conv_x6_pack_batch_end_lanes");
+#if defined(__HIP__)
+    if (ev) {
+        if (hipEventRecord(ev->join, side_stream) != hipSuccess) {
+            ssn_set_error("conv x6 pack batch: join record failed: %s", hipGetErrorString(hipGetLastError()));
+            return SSN_ERR_LAUNCH;
+        }
+        ev->pending = true;
+    }
+#endif
+    return SSN_OK;
+}
+}  // namespace
+
+extern "C" int ssn_conv_x6_pack_batch_end(void* plan, long plan_bytes, int force_write, hipStream_t stream) {
+    return pack_batch_run(plan, plan_bytes, force_write, -1, stream, nullptr);
+}
+// The same with the recorded entries in two parts: the first n_first (the stem's: the only operands the first launches of a pass
+// read) are cleared, measured and packed on `stream`; the others on `side_stream`, forked behind the plan writes of `stream`,
+// with a join event recorded behind them that ssn_conv_x6_pack_batch_join makes a stream wait for.  The events are created once
+// per device, without timing, never inside a capture (a first call on a capturing stream keeps to `stream`).  n_first == the
+// number of recorded entries, or a null side_stream: exactly ssn_conv_x6_pack_batch_end.  Same bytes in every case.
+extern "C" int ssn_conv_x6_pack_batch_end_lanes(void* plan, long plan_bytes, int force_write, int n_first, hipStream_t stream,
+                                                hipStream_t side_stream) {
+    if (n_first < 0) {
+        ssn_conv_x6_pack_batch_abort();
+        ssn_set_error("conv x6 pack batch: %d leading entries", n_first);
+        return SSN_ERR_ARG;
+    }
+    return pack_batch_run(plan, plan_bytes, force_write, n_first, stream, side_stream);
+}
+// `stream` waits for the side part of the last split packing pass; nothing pending: nothing happens.
+extern "C" int ssn_conv_x6_pack_batch_join(hipStream_t stream) {
+#if defined(__HIP__)
+    std::lock_guard<std::mutex> lock(g_pack_lane_mu);
+    PackLaneEvents* ev = pack_lane_events(nullptr);
+    if (ev && ev->pending) {
+        ev->pending = false;
+        if (hipStreamWaitEvent(stream, ev->join, 0) != hipSuccess) {
+            ssn_set_error("conv x6 pack batch: join failed: %s", hipGetErrorString(hipGetLastError()));
+            return SSN_ERR_LAUNCH;
+        }
+    }
+#else
+    (void)stream;
+#endif
     return SSN_OK;
 }
 

@@ -213,10 +213,19 @@ class PackBatch:
     in three launches through a device-resident plan (ssn_conv_x6_pack_batch_end).  `state` is a dict the caller keeps (one per
     backbone and kind of pass): it holds the operand buffers -- the k-th allocation of a batch gets the same buffer every time, so
     the recorded entries repeat from step to step and the plan is written once -- and the plan buffer.  The returned operands are
-    valid after the block; they are overwritten by the next batch on the same state (same weights -> same contents)."""
+    valid after the block; they are overwritten by the next batch on the same state (same weights -> same contents).
 
-    def __init__(self, state, device):
+    `side` (a torch.cuda.Stream) with leading entries marked by stem_done() (or given as `n_first`): leaving the block issues those
+    leading entries on the current stream and all others on `side` (ssn_conv_x6_pack_batch_end_lanes); the operands recorded behind
+    the mark are valid on the current stream only after pack_batch_join().  No mark or no `side`: one stream."""
+
+    def __init__(self, state, device, n_first=None, side=None):
         self.state, self.device, self.k = state, device, 0
+        self.n_first, self.side = n_first, side
+
+    def stem_done(self):
+        """everything recorded so far belongs to the launches that run beside the side stream's part"""
+        self.n_first = int(self.lib.cdll.ssn_conv_x6_pack_batch_entries())
 
     def take(self, nfloats, device):
         bufs = self.state.setdefault("bufs", [])
@@ -248,9 +257,20 @@ class PackBatch:
         if need and (plan is None or plan.numel() < need or plan.device != self.device):
             plan = self.state["plan"] = torch.empty(max(need, 1 << 16), device=self.device, dtype=torch.uint8)
             fresh = 1
-        self.lib.call("ssn_conv_x6_pack_batch_end", _p(plan), plan.numel() if plan is not None else 0, fresh,
-                      _stream(self.lib, plan) if plan is not None else None)
+        stream = _stream(self.lib, plan) if plan is not None else None
+        if self.side is not None and self.n_first is not None and plan is not None:
+            # (the emulator has no streams: any non-null value splits the launches)
+            side = 1 if self.lib.is_emulator else self.side.cuda_stream
+            self.lib.call("ssn_conv_x6_pack_batch_end_lanes", _p(plan), plan.numel(), fresh, int(self.n_first), stream, side)
+        else:
+            self.lib.call("ssn_conv_x6_pack_batch_end", _p(plan), plan.numel() if plan is not None else 0, fresh, stream)
         return False
+
+
+def pack_batch_join(device):
+    """The current stream of `device` waits for the side part of the last split PackBatch (nothing pending: nothing happens)."""
+    lib = _lib.get_lib()
+    lib.call("ssn_conv_x6_pack_batch_join", None if lib.is_emulator else torch.cuda.current_stream(device).cuda_stream)
 
 
 def pack_weights_multi(entries, x6=False):

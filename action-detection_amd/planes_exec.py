@@ -327,18 +327,32 @@ def run_forward(net, x, keep):
         # would have saved) -- recorded and issued in three launches (kernels.PackBatch; one state per kind of pass so that the
         # operand buffers, and with them the device-resident plan, repeat from step to step)
         pstate = net.__dict__.setdefault("_pack_states", {}).setdefault((dev, bool(keep), tuple(x.shape[1:])), {})
-        batch = K.PackBatch(pstate, dev) if net.batch_packing else contextlib.nullcontext()
+        # net.pack_lanes: the stem's operand (recorded first) on this stream, all others on the side stream beside the stem's
+        # launches; launch_all joins in front of the first launch that reads one of them
+        stem_op = plan[0] if (plan and plan[0]["kind"] == "conv" and plan[0]["src"] == "data") else None
+        pack_side = (net._side_stream(dev) if (net.batch_packing and net.pack_lanes and net.branch_lanes and x.is_cuda
+                                               and stem_op is not None) else None)
+        batch = K.PackBatch(pstate, dev, side=pack_side) if net.batch_packing else contextlib.nullcontext()
         with batch:
             packed = {}
-            for op in conv_ops:
-                if op["s2d"]:
-                    packed[op["lids"][0]] = K.pack_weights_rect(K.s2d_weights(getattr(net, op["lids"][0]).weight.detach()))
-            rect_ops = [op for op in conv_ops if op["rect"] and not op["s2d"]]
-            packed.update(zip((op["lids"][0] for op in rect_ops),
-                              K.pack_rect_multi([getattr(net, op["lids"][0]).weight.detach() for op in rect_ops])))
-            sq_ops = [op for op in conv_ops if not op["rect"] and not op["s2d"]]
-            packed.update(zip((op["lids"][0] for op in sq_ops), K.pack_weights_multi(
-                [([getattr(net, lid).weight.detach() for lid in op["lids"]], 0) for op in sq_ops], x6=True)))
+
+            def pack_fwd(ops):
+                for op in ops:
+                    if op["s2d"]:
+                        packed[op["lids"][0]] = K.pack_weights_rect(K.s2d_weights(getattr(net, op["lids"][0]).weight.detach()))
+                rect_ops = [op for op in ops if op["rect"] and not op["s2d"]]
+                packed.update(zip((op["lids"][0] for op in rect_ops),
+                                  K.pack_rect_multi([getattr(net, op["lids"][0]).weight.detach() for op in rect_ops])))
+                sq_ops = [op for op in ops if not op["rect"] and not op["s2d"]]
+                packed.update(zip((op["lids"][0] for op in sq_ops), K.pack_weights_multi(
+                    [([getattr(net, lid).weight.detach() for lid in op["lids"]], 0) for op in sq_ops], x6=True)))
+
+            if pack_side is not None:
+                pack_fwd([stem_op])
+                batch.stem_done()
+                pack_fwd([op for op in conv_ops if op is not stem_op])
+            else:
+                pack_fwd(conv_ops)
             if keep:
                 packed_dg = _pack_dgrad(net, plan)
         if ckey is not None:
@@ -458,7 +472,13 @@ def run_forward(net, x, keep):
         side_ops, joins = _branch_lanes(plan) if (net.branch_lanes and x.is_cuda) else ({}, set())
         side = net._side_stream(dev) if side_ops else None
         main = torch.cuda.current_stream(dev) if side_ops else None
+        # a packing pass split over two streams (net.pack_lanes): the stem convolution and the pool behind it read the stem's
+        # operand only; everything else waits for the side stream's part (a repeated pass finds nothing pending)
+        pack_join = 1 if (len(plan) > 1 and plan[1]["kind"] == "pool" and plan[1]["pool"] != "avg"
+                          and plan[1]["src"] == plan[0]["dst"]) else 0
         for pidx, op in enumerate(plan):
+            if pidx == pack_join + 1 and x.is_cuda:
+                K.pack_batch_join(dev)
             if pidx in joins:
                 main.wait_stream(side)
             if pidx in side_ops:
@@ -471,6 +491,8 @@ def run_forward(net, x, keep):
                 run_op(op)
         if side_ops:
             main.wait_stream(side)
+        if len(plan) <= pack_join + 1 and x.is_cuda:
+            K.pack_batch_join(dev)
         return feat_box[0]
 
     # delayed scales: this pass stores with the scales derived from the previous pass's maxima
@@ -605,7 +627,10 @@ def run_backward(net, dfeat, saved, hook=True):
         if not (net.wgrad_lanes and net.group_wgrad):
             wl_streams = None
         elif dfeat.is_cuda and net.overlap_wgrad and net.branch_lanes:
-            wl_streams = net._wgrad_streams(dev, 3)
+            # (torch hands out streams from a pool of 32 per device, round-robin: in a process that has created many, one of these
+            # can BE the stream this pass runs on -- that one is left out; where a family runs does not change its bits)
+            cur = torch.cuda.current_stream(dev).cuda_stream
+            wl_streams = [s for s in net._wgrad_streams(dev, 3) if s.cuda_stream != cur]
         else:
             wl_streams = []
 

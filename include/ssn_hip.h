@@ -145,6 +145,13 @@ int ssn_conv_x6_pack_batch_entries(void);
 long ssn_conv_x6_pack_entry_bytes(void);
 void ssn_conv_x6_pack_batch_abort(void);
 int ssn_conv_x6_pack_batch_end(void* plan, long plan_bytes, int force_write, hipStream_t stream);
+/* _end in two parts: the first n_first recorded entries (the stem's) on `stream`, the others on `side_stream`, forked behind the
+ * plan writes of `stream`; a join event is recorded behind them, and ssn_conv_x6_pack_batch_join makes a stream wait for it (no
+ * pending join: a no-op).  Events: once per device, no timing, never created inside a capture.  n_first == entries or a null
+ * side_stream: exactly _end.  The packed bytes do not depend on where an entry runs. */
+int ssn_conv_x6_pack_batch_end_lanes(void* plan, long plan_bytes, int force_write, int n_first, hipStream_t stream,
+                                     hipStream_t side_stream);
+int ssn_conv_x6_pack_batch_join(hipStream_t stream);
 int ssn_conv_x6_fwd(const float* x, const float* w_packed, const float* scale, const float* shift, float* y, int N,
                     int Cin, int H, int W, long x_img_stride, int Cout, int Ho, int Wo, long y_img_stride,
                     int ksize, int stride, int pad, int relu, int x_guard_bytes, int tile_cfg, const float* x_amax,
